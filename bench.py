@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the NCuts hot path on MI355X (contract in the project brief, section (4)).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks
@@ -438,6 +438,28 @@ def dry_run(args, world, rank):
         dist.destroy_process_group()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, merged: dict) -> None:
+    """What the timed path returned in its last step, as .npy files under `out_dir`: `labels.npy` (float32, one row of
+    N_POINTS labels per chunk, chunks in world order), `chunk_ids.npy` (float64, the world chunk index of each row) and
+    `n_groups.npy` (float64, the number of groups of each row).  The inputs are a function of the arguments alone (chunk c
+    is the synthetic chunk of seed c mod chunks per rank), so two builds run with the same arguments can be compared file for
+    file.  Past 64 MB in all, a fixed (seed 0) sample of whole chunks is written instead of every chunk."""
+    ids = sorted(merged)
+    row_bytes = N_POINTS * 4 + 16
+    keep = max(1, DUMP_LIMIT_BYTES // row_bytes)
+    if len(ids) > keep:
+        pick = np.random.default_rng(0).choice(len(ids), size=keep, replace=False)
+        ids = [ids[i] for i in sorted(pick)]
+    labels = np.stack([np.asarray(merged[c]) for c in ids])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "labels.npy"), labels.astype(np.float32))
+    np.save(os.path.join(out_dir, "chunk_ids.npy"), np.asarray(ids, dtype=np.float64))
+    np.save(os.path.join(out_dir, "n_groups.npy"), np.asarray([np.unique(l).size for l in labels], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -454,7 +476,11 @@ def main():
     ap.add_argument("--no-host-inputs", action="store_true", help="skip the pinned-host-input leg (value_host_inputs)")
     ap.add_argument("--no-latency-all", action="store_true", help="skip the one-chunk-alone pass over all chunks of the step (profiled runs)")
     ap.add_argument("--dry", action="store_true", help="CPU-only rehearsal of the multi-rank plumbing (gloo), no compute")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the label array of every chunk) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # nothing GPU-related has been imported yet: the ranks are fresh child processes
@@ -741,6 +767,8 @@ def main():
         run_steps(args.warmup)
     elapsed, last = timed(args.steps)
     res, merged = last
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, merged)
     nnz = res[0][3]
     stb = res[0][2]
 

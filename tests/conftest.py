@@ -17,7 +17,14 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session", autouse=True)
 def _built_library():
-    """The suites need libautoinst_hip.so; build it (hipcc cross-compiles without a GPU) if it is missing."""
+    """The suites need libautoinst_hip.so; build it (hipcc cross-compiles without a GPU) if it is missing.
+
+    torch ships its own HIP runtime, and in one process it must be initialised before the library is loaded
+    (autoinst_amd/_ffi.py): otherwise a CPU test that loads the library first leaves every later GPU test without a
+    device when the whole suite runs at once.  So torch takes the device here, before any test touches the library."""
+    import torch
+    if torch.cuda.is_available():
+        torch.cuda.init()
     lib = os.path.join(ROOT, "autoinst_amd", "libautoinst_hip.so")
     if not os.path.exists(lib):
         import __graft_entry__

@@ -103,3 +103,39 @@ def test_first_collective_that_never_completes_ends_the_rank_non_zero_and_names_
     assert procs[0].returncode == 75, (procs[0].returncode, err0[-1500:])
     assert "rank 0 of 2" in err0 and "did not complete" in err0 and "NOT REACHED" not in out0
     assert took < 60
+
+
+def test_dump_outputs_writes_the_last_step_labels(tmp_path):
+    """`bench.py --dump-outputs DIR`: float32 labels of every chunk in world order, with their chunk ids and group counts."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    merged = {c: rng.integers(0, 40, bench.N_POINTS).astype(np.int32) for c in (3, 0, 2, 1)}
+    bench.dump_outputs(str(tmp_path / "out"), merged)
+    lab = np.load(tmp_path / "out" / "labels.npy")
+    ids = np.load(tmp_path / "out" / "chunk_ids.npy")
+    ng = np.load(tmp_path / "out" / "n_groups.npy")
+    assert lab.dtype == np.float32 and ids.dtype == np.float64 and ng.dtype == np.float64
+    assert ids.tolist() == [0, 1, 2, 3] and lab.shape == (4, bench.N_POINTS)
+    assert all(np.array_equal(lab[i], merged[i]) for i in range(4))
+    assert ng.tolist() == [float(np.unique(merged[i]).size) for i in range(4)]
+
+
+def test_dump_outputs_stays_under_64_mb(tmp_path, monkeypatch):
+    """Past the limit a fixed sample of whole chunks is written, the same one every time."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "N_POINTS", 1000)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * (1000 * 4 + 16))
+    merged = {c: np.full(1000, c, dtype=np.int32) for c in range(50)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), merged)
+    ids = np.load(tmp_path / "a" / "chunk_ids.npy")
+    assert ids.size == 10 and np.array_equal(ids, np.load(tmp_path / "b" / "chunk_ids.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "labels.npy")[:, 0], ids)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64 << 20
