@@ -15,4 +15,8 @@ def __getattr__(name):
     if name in ("Metrics", "score", "label_pairs", "merge_chunks_unite_instances2", "merge_associate", "unique_points"):
         from . import labels_api as _l
         return getattr(_l, name)
+    if name in ("box_select", "statistical_inlier_indices", "voxel_down_sample", "chunks_from_pointcloud",
+                "chunk_and_downsample_point_clouds"):
+        from . import prep_api as _p
+        return getattr(_p, name)
     raise AttributeError(name)

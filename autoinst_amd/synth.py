@@ -119,3 +119,123 @@ def synthetic_chunk(n: int, seed: int = 0, tarl: bool = True, dino: bool = False
     if dino:
         out["dino"] = surrogate_features(gt, 384, seed + 1, zero_frac=0.05)
     return out
+
+
+def _jittered_grid(rng, u0, u1, v0, v1, step):
+    """One point per step x step cell of the rectangle [u0, u1) x [v0, v1), uniform inside its cell (a minor-voxel surface)."""
+    u = np.arange(u0, u1, step)
+    v = np.arange(v0, v1, step)
+    uu, vv = np.meshgrid(u, v, indexing="ij")
+    uu = uu.ravel() + rng.random(uu.size) * step
+    vv = vv.ravel() + rng.random(vv.size) * step
+    return uu, vv
+
+
+def street_map(length: float = 120.0, seed: int = 0, *, step: float = 0.05, width: float = 16.0, facade_height: float = 8.0,
+               n_objects: int | None = None, outlier_frac: float = 0.01):
+    """A deterministic street in the shape of the minor-voxel maps ``chunk_and_downsample_point_clouds`` takes
+    (``dataset_utils.py:489``): one point per ``step`` (0.05 m, ``MINOR_VOXEL_SIZE``) cell of every surface.
+
+    In the map's frame the street runs along x over [0, length]: a ground plane |y| <= width / 2 (the ground cloud), two
+    facades at y = +-width / 2 up to ``facade_height`` and box-shaped objects on the road (the non-ground cloud), plus
+    ``outlier_frac`` uniform outliers in the box [0, length] x [-width, width] x [-2, 3 facade_height] (some metres from
+    everything) and a few points repeated 24 times each (so that the outlier filter's ``avg == 0`` rule fires).  Both clouds
+    are shuffled, as a hash-ordered voxel map is.  The trajectory runs along the street centre at 1.7 m in the world frame
+    ``T_pcd`` (a rotation about z and a tilt, then a shift); points on the chunk boxes' x faces (exactly) test the strict crop.
+
+    Returns a dict: ``nonground``, ``ground`` (n, 3) float64; ``labels`` with ``seg_nonground``, ``instance_nonground``,
+    ``seg_ground``, ``instance_ground`` (int32: semantic 40 road, 50 building, 10 object, 0 outlier; instance = object
+    number from 1, else 0); ``T_pcd`` (4, 4); ``positions`` (P, 3) world; ``first_position``; ``indices`` (P,) int64.
+    """
+    rng = np.random.default_rng(seed)
+    half = width / 2.0
+    # ground
+    gx, gy = _jittered_grid(rng, 0.0, length, -half, half, step)
+    gz = 0.02 * np.sin(gx * 0.3) + 0.01 * rng.standard_normal(gx.size)
+    ground = np.stack([gx, gy, gz], 1)
+    # facades
+    parts, sem, inst = [], [], []
+    for side in (-1.0, 1.0):
+        fx, fz = _jittered_grid(rng, 0.0, length, 0.0, facade_height, step)
+        fy = side * half + 0.01 * rng.standard_normal(fx.size)
+        parts.append(np.stack([fx, fy, fz], 1))
+        sem.append(np.full(fx.size, 50, np.int32))
+        inst.append(np.zeros(fx.size, np.int32))
+    # objects: boxes on the road, their 5 visible faces sampled at the same density
+    n_objects = int(length / 6.0) if n_objects is None else n_objects
+    for o in range(n_objects):
+        c = np.array([rng.uniform(2.0, length - 2.0), rng.uniform(-half + 2.0, half - 2.0), 0.0])
+        s = np.array([rng.uniform(1.5, 4.5), rng.uniform(1.2, 2.0), rng.uniform(1.0, 2.2)])
+        lo = c - np.array([s[0] / 2, s[1] / 2, 0.0])
+        faces = []
+        for axis in range(3):
+            a, b = [d for d in range(3) if d != axis]
+            for end in ((0, 1) if axis < 2 else (1,)):
+                u, v = _jittered_grid(rng, 0.0, s[a], 0.0, s[b], step)
+                f = np.empty((u.size, 3))
+                f[:, a] = lo[a] + u
+                f[:, b] = lo[b] + v
+                f[:, axis] = lo[axis] + end * s[axis]
+                faces.append(f)
+        f = np.concatenate(faces)
+        parts.append(f)
+        sem.append(np.full(f.shape[0], 10, np.int32))
+        inst.append(np.full(f.shape[0], o + 1, np.int32))
+    nonground = np.concatenate(parts)
+    seg_ng, inst_ng = np.concatenate(sem), np.concatenate(inst)
+    # uniform outliers
+    n_out = int(outlier_frac * (nonground.shape[0] + ground.shape[0]))
+    out = np.stack([rng.uniform(0.0, length, n_out), rng.uniform(-width, width, n_out),
+                    rng.uniform(-2.0, 3.0 * facade_height, n_out)], 1)
+    nonground = np.concatenate([nonground, out])
+    seg_ng = np.concatenate([seg_ng, np.zeros(n_out, np.int32)])
+    inst_ng = np.concatenate([inst_ng, np.zeros(n_out, np.int32)])
+    seg_g = np.full(ground.shape[0], 40, np.int32)
+    inst_g = np.zeros(ground.shape[0], np.int32)
+    # trajectory: one position per metre along the centre line (with a little lateral noise), in the world frame
+    ang, tilt = 0.6, 0.02
+    Rz = np.array([[np.cos(ang), -np.sin(ang), 0.0], [np.sin(ang), np.cos(ang), 0.0], [0.0, 0.0, 1.0]])
+    Rx = np.array([[1.0, 0.0, 0.0], [0.0, np.cos(tilt), -np.sin(tilt)], [0.0, np.sin(tilt), np.cos(tilt)]])
+    T_pcd = np.eye(4)
+    T_pcd[:3, :3] = Rz @ Rx
+    T_pcd[:3, 3] = [351.25, -72.5, 3.0]
+    s_path = np.arange(0.0, length, 1.0)
+    p_map = np.stack([s_path, 0.05 * rng.standard_normal(s_path.size), np.full(s_path.size, 1.7)], 1)
+    positions = p_map @ T_pcd[:3, :3].T + T_pcd[:3, 3]
+    first_position = T_pcd[:3, 3].copy()
+    indices = np.arange(s_path.size, dtype=np.int64) * 5
+
+    # points exactly on the x faces of the chunk boxes (the crop is strict: they belong to no box through that face)
+    from .prep_api import chunk_centres
+    from .config import CHUNK_SIZE
+    centres, _ = chunk_centres(T_pcd, positions, first_position, indices)
+    extra_ng, extra_g = [], []
+    for c in centres:
+        for xf in (c[0] - 0.5 * CHUNK_SIZE[0], c[0] + 0.5 * CHUNK_SIZE[0]):
+            for cloud, extra in ((nonground, extra_ng), (ground, extra_g)):
+                near = cloud[np.abs(cloud[:, 0] - xf) < 0.5]
+                pick = near[rng.choice(near.shape[0], size=min(40, near.shape[0]), replace=False)].copy()
+                pick[:, 0] = xf
+                extra.append(pick)
+    if extra_ng:
+        e = np.concatenate(extra_ng)
+        nonground = np.concatenate([nonground, e])
+        seg_ng = np.concatenate([seg_ng, np.full(e.shape[0], 50, np.int32)])
+        inst_ng = np.concatenate([inst_ng, np.zeros(e.shape[0], np.int32)])
+        e = np.concatenate(extra_g)
+        ground = np.concatenate([ground, e])
+        seg_g = np.concatenate([seg_g, np.full(e.shape[0], 40, np.int32)])
+        inst_g = np.concatenate([inst_g, np.zeros(e.shape[0], np.int32)])
+
+    def dup_and_shuffle(p, s_, i_):
+        d = rng.choice(p.shape[0], size=max(1, p.shape[0] // 20000), replace=False)
+        rep = np.repeat(d, 23)   # each picked point 24 times in all
+        p, s_, i_ = np.concatenate([p, p[rep]]), np.concatenate([s_, s_[rep]]), np.concatenate([i_, i_[rep]])
+        perm = rng.permutation(p.shape[0])
+        return np.ascontiguousarray(p[perm]), s_[perm], i_[perm]
+
+    nonground, seg_ng, inst_ng = dup_and_shuffle(nonground, seg_ng, inst_ng)
+    ground, seg_g, inst_g = dup_and_shuffle(ground, seg_g, inst_g)
+    labels = {"seg_nonground": seg_ng, "instance_nonground": inst_ng, "seg_ground": seg_g, "instance_ground": inst_g}
+    return {"nonground": nonground, "ground": ground, "labels": labels, "T_pcd": T_pcd, "positions": positions,
+            "first_position": first_position, "indices": indices}

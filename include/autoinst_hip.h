@@ -282,6 +282,37 @@ int ai_merge_associate(ai_ctx* ctx, const double* map_xyz, const int32_t* map_in
 int ai_unique_points(ai_ctx* ctx, const double* xyz, int64_t n, int mem_kind, int32_t* keep_index, int64_t* n_keep);
 
 /*
+ * The step that produces the chunks: chunk_and_downsample_point_clouds (pipeline/dataset/dataset_utils.py:489-567, called at
+ * run_pipeline.py:129), per chunk and per cloud (non-ground / ground).  xyz and the index / point outputs are host or device
+ * according to mem_kind; counts, offsets and stats are HOST values.  Indices are int32 (n < 2^30; box select: n < 2^31 - 256).
+ *
+ * ai_box_select: the crop of chunk_generation.py:134-137 for n_boxes boxes at once.  boxes (HOST, n_boxes x 6 doubles: lo x, y,
+ *   z, hi x, y, z); a point is inside box b iff lo < p < hi on all three axes (strict).  out_index receives, box after box, the
+ *   ascending indices of the points inside each box; box_offsets (HOST, n_boxes + 1) the start of each box's run and the total.
+ *   *n_total is always the full count: when it exceeds cap nothing is written to out_index (call again with cap >= *n_total).
+ *
+ * ai_statistical_inliers: open3d 0.17 PointCloud::RemoveStatisticalOutliers (pipeline/utils/point_cloud/point_cloud_utils.py:
+ *   198-202, called at chunk_generation.py:143) as it is written: k = min(nb_neighbors, n); avg[i] = the mean of the Euclidean
+ *   distances of the k nearest points of i (i itself included, at distance 0), summed in ascending order; mean = (sum of the
+ *   avg > 0) / n (all n points in the denominator); std = sqrt(sum over avg > 0 of (avg - mean)^2 / (n - 1)); i is kept iff
+ *   avg[i] > 0 && avg[i] < mean + std_ratio * std.  keep_index (capacity n) receives the kept indices in ascending order and
+ *   *n_keep their number.  avg_out (n, per mem_kind) and stats_out (HOST: mean, std, threshold) may be NULL.  nb_neighbors < 1,
+ *   std_ratio <= 0, or k > 64 is AI_ERR_BAD_ARG; n = 0 keeps nothing (stats_out is not written).  Reproducible bit for bit.
+ *
+ * ai_voxel_down_sample: open3d PointCloud::VoxelDownSample (dataset_utils.py:534-535): vmin = min_bound - voxel_size / 2, voxel
+ *   of p = floor((p - vmin) / voxel_size), output point = sum of the voxel's points in input-index order / their count.  Output
+ *   order: ascending (ix, iy, iz) (open3d's is the order of a hash map).  out_xyz (capacity n x 3), trace (n, may be NULL: the
+ *   output row of every input point); *n_out = number of voxels.  voxel_size <= 0, or a voxel index outside the int range
+ *   (open3d's "voxel_size is too small"), is AI_ERR_BAD_ARG.
+ */
+int ai_box_select(ai_ctx* ctx, const double* xyz, int64_t n, const double* boxes, int32_t n_boxes, int mem_kind,
+                  int64_t cap, int32_t* out_index, int64_t* box_offsets, int64_t* n_total);
+int ai_statistical_inliers(ai_ctx* ctx, const double* xyz, int64_t n, int32_t nb_neighbors, double std_ratio,
+                           int mem_kind, int32_t* keep_index, int64_t* n_keep, double* avg_out, double* stats_out);
+int ai_voxel_down_sample(ai_ctx* ctx, const double* xyz, int64_t n, double voxel_size, int mem_kind, double* out_xyz,
+                         int64_t* n_out, int32_t* trace);
+
+/*
  * Timing hook for bench.py: runs `reps` fused Lanczos SpMV steps on the whole graph as
  * one segment and returns the average kernel time (HIP events on the context's stream)
  * plus the algorithmic byte count of one launch.
