@@ -158,6 +158,13 @@ class Flow {
 #else
   static constexpr int inject = -1;
 #endif
+#ifdef AI_TEST_HOOKS
+  const char* dump_path = getenv("AI_FLOW_DUMP");  // one record per harvested / component-split segment appended here (dump_seg)
+  DevBuf<double> w_costs;                           // the wave's 10 costs per segment as fk_sweep_final formed them
+  double* dump_costs() { return dump_path ? w_costs.p : nullptr; }
+#else
+  double* dump_costs() { return nullptr; }
+#endif
   long long n_above_limit = 0;     // Ritz pairs accepted above the limit because the repeated solve reproduced the residual bit for bit
   unsigned long long n_check_timeouts = 0;  // fk_check judging blocks that gave up waiting for the launch's scanning blocks
   long long n_harvested = 0;
@@ -446,6 +453,9 @@ class Flow {
     AI_TRY(pmm.alloc((size_t)CLIST));
     AI_TRY(w_scale.alloc((size_t)WCAP));
     AI_TRY(w_thr.alloc((size_t)WCAP * AI_NUM_CUTS));
+#ifdef AI_TEST_HOOKS
+    if (dump_path) AI_TRY(w_costs.alloc((size_t)WCAP * AI_NUM_CUTS));
+#endif
     AI_TRY(w_vol.alloc((size_t)WCAP));
     AI_TRY(w_nosplit.alloc((size_t)WCAP));
     AI_TRY(w_ncomp.alloc((size_t)WCAP));
@@ -963,7 +973,7 @@ class Flow {
                          (const uint8_t*)bin.p, psweep.p);
       AI_KERNEL_CHECK();
       hipLaunchKernelGGL(fk_sweep_final, dim3((unsigned)nA), dim3(AI_BLOCK), 0, sw, (const SegRec*)wrecP.p, (const int32_t*)w_nosplit.p,
-                         (const double*)psweep.p, T, pr_i + 2 * nA, pr_i, pr_i + nA, pr_mcut);
+                         (const double*)psweep.p, T, pr_i + 2 * nA, pr_i, pr_i + nA, pr_mcut, dump_costs());
       AI_KERNEL_CHECK();
     }
     if (!wM.empty()) {
@@ -1041,6 +1051,60 @@ class Flow {
 #endif
     fclose(f);
   }
+#ifdef AI_TEST_HOOKS
+  // (test-only build, AI_FLOW_DUMP) one record per segment of the wave, appended to the file before stage 3 permutes any row: the stage-2
+  // event has completed, fk_partition has not run.  Fixed little-endian layout (tests/flow_dump.py reads it):
+  //   int64  kind ('L' = 76: harvested Lanczos segment, 'C' = 67: split into its connected components), chunk, n, m, restarts, nosplit,
+  //          kstar, split, ntrue
+  //   double theta (as the host used it), resid (estimate), true resid (fk_resid_final), scale, mcut, thr[10] (fk_minmax_final),
+  //          costs[10] (fk_sweep_final)
+  //   int32  ids[n]: chunk-local original ids of the rows in position order (G.orig[par])
+  //   L: double ev[n], fk_ritz's raw vector at those positions | C: int32 comp[n], the device's component label per row
+  // A C record leaves every field after n at 0.  A rejected Ritz pair that is solved again is not dumped; its repeat is.
+  struct DumpHead {
+    int64_t kind, chunk, n, m, restarts, nosplit, kstar, split, ntrue;
+    double theta, resid, rtrue, scale, mcut, thr[AI_NUM_CUTS], costs[AI_NUM_CUTS];
+  };
+  int dump_seg(const FSeg& s, DumpHead& h, int wi) {
+    h.chunk = s.chunk;
+    h.n = s.n;
+    std::vector<int32_t> ids((size_t)s.n), comp;
+    std::vector<double> v;
+    AI_HIP(hipMemcpyAsync(ids.data(), G.orig[s.par] + s.g0, (size_t)s.n * sizeof(int32_t), hipMemcpyDeviceToHost, sw));
+    if (wi < 0) {
+      h.kind = 'C';
+      comp.resize((size_t)s.n);
+      AI_HIP(hipMemcpyAsync(comp.data(), parent.p + s.g0, (size_t)s.n * sizeof(int32_t), hipMemcpyDeviceToHost, sw));
+    } else {
+      int32_t ns = 0;
+      h.kind = 'L';
+      h.m = s.m;
+      h.restarts = s.restarts;
+      v.resize((size_t)s.n);
+      AI_HIP(hipMemcpyAsync(v.data(), ev.p + s.g0, (size_t)s.n * sizeof(double), hipMemcpyDeviceToHost, sw));
+      AI_HIP(hipMemcpyAsync(&h.theta, coef_d.p + wA.size() + wi, sizeof(double), hipMemcpyDeviceToHost, sw));
+      AI_HIP(hipMemcpyAsync(&h.scale, w_scale.p + wi, sizeof(double), hipMemcpyDeviceToHost, sw));
+      AI_HIP(hipMemcpyAsync(&ns, w_nosplit.p + wi, sizeof(int32_t), hipMemcpyDeviceToHost, sw));
+      AI_HIP(hipMemcpyAsync(h.thr, w_thr.p + (size_t)wi * AI_NUM_CUTS, sizeof h.thr, hipMemcpyDeviceToHost, sw));
+      AI_HIP(hipMemcpyAsync(h.costs, w_costs.p + (size_t)wi * AI_NUM_CUTS, sizeof h.costs, hipMemcpyDeviceToHost, sw));
+      h.nosplit = ns;
+    }
+    AI_HIP(hipStreamSynchronize(sw));
+    FILE* f = fopen(dump_path, "ab");
+    if (!f) {
+      ai_set_error("AI_FLOW_DUMP: %s cannot be opened", dump_path);
+      return AI_ERR_BAD_ARG;
+    }
+    bool ok = fwrite(&h, sizeof h, 1, f) == 1 && fwrite(ids.data(), sizeof(int32_t), ids.size(), f) == ids.size();
+    ok = ok && (wi < 0 ? fwrite(comp.data(), sizeof(int32_t), comp.size(), f) == comp.size() : fwrite(v.data(), sizeof(double), v.size(), f) == v.size());
+    ok = (fclose(f) == 0) && ok;
+    if (!ok) {
+      ai_set_error("AI_FLOW_DUMP: writing %s failed", dump_path);
+      return AI_ERR_BAD_ARG;
+    }
+    return AI_OK;
+  }
+#endif
   int wave_s3() {
     wpin_off = 0;
     const size_t nA = wA.size();
@@ -1101,6 +1165,18 @@ class Flow {
         if (guard_log && s.restarts > 0 && hist_copy.size()) guard_dump("REPEAT", i, nA, s, r_resid[i], r_true[i]);
         if (r_resid[i] <= opt.tol && r_true[i] > true_resid_limit) ++n_above_limit;  // (accepted: the repeat reproduced it bit for bit)
         max_true_resid = std::max(max_true_resid, r_true[i]);  // of the pairs that are CUT (a rejected pair is not)
+#ifdef AI_TEST_HOOKS
+        if (dump_path) {
+          DumpHead h{};
+          h.resid = r_resid[i];
+          h.rtrue = r_true[i];
+          h.mcut = r_mcut[i];
+          h.kstar = r_kstar[i];
+          h.split = r_split[i];
+          h.ntrue = r_ntrue[i];
+          AI_TRY(dump_seg(s, h, (int)i));
+        }
+#endif
         if (!r_split[i]) {
           leaf(s.g0);
           continue;
@@ -1154,6 +1230,12 @@ class Flow {
       ccont.assign((size_t)w_ncomp_all, 0);
       size_t ti = 0;
       for (const FSeg& s : wM) {
+#ifdef AI_TEST_HOOKS
+        if (dump_path) {
+          DumpHead h{};
+          AI_TRY(dump_seg(s, h, -1));
+        }
+#endif
         int offp = 0;
         while (ti < h_troot.size() && h_troot[ti] < s.g0 + s.n) {
           const int nc = h_tsize[ti];

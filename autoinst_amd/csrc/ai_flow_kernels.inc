@@ -1541,9 +1541,7 @@ __global__ void fk_minmax_final(const SegRec* __restrict__ recs, const MinMaxPar
   const double mn = (sc > 0.0) ? r.mn * sc : r.mx * sc;
   const double mx = (sc > 0.0) ? r.mx * sc : r.mn * sc;
   scale[s] = sc;
-  nosplit[s] = (fabs(mn - mx) <= 1e-8 + 1e-5 * fabs(mx)) ? 1 : 0;
-  const double step = __ddiv_rn(__dsub_rn(mx, mn), 10.0);
-  for (int k = 0; k < AI_NUM_CUTS; ++k) thr[s * AI_NUM_CUTS + k] = __dadd_rn(__dmul_rn((double)k, step), mn);
+  nosplit[s] = mm_thresholds(mn, mx, thr + s * AI_NUM_CUTS);
 }
 
 __global__ __launch_bounds__(AI_BLOCK) void fk_sweep(const Task* __restrict__ ftasks, const int32_t* __restrict__ nosplit, FlowCsr G,
@@ -1621,12 +1619,13 @@ __global__ __launch_bounds__(AI_BLOCK) void fk_sweep(const Task* __restrict__ ft
   }
 }
 
-// per record i: the 10 costs, first strictly smaller wins, split iff mcut < T (res_*: what the host reads back)
+// per record i: the 10 costs, first strictly smaller wins, split iff mcut < T (res_*: what the host reads back; res_costs[i][10]:
+// the costs themselves, written only when non-null -- the test-only per-segment dump, Flow::dump_seg; the shipped driver passes null)
 __global__ __launch_bounds__(AI_BLOCK) void fk_sweep_final(const SegRec* __restrict__ recs,
                                                            const int32_t* __restrict__ nosplit, const double* __restrict__ part, double T,
                                                            int32_t* __restrict__ kstar,
                                                            int32_t* __restrict__ res_split, int32_t* __restrict__ res_ntrue,
-                                                           double* __restrict__ res_mcut) {
+                                                           double* __restrict__ res_mcut, double* __restrict__ res_costs) {
   __shared__ double acc[SWF_STRIPES][AI_SWEEP_VALS];
   const int i = blockIdx.x;
   const int s = i;
@@ -1638,6 +1637,8 @@ __global__ __launch_bounds__(AI_BLOCK) void fk_sweep_final(const SegRec* __restr
       res_split[i] = 0;
       res_ntrue[i] = 0;
       res_mcut[i] = INFINITY;
+      if (res_costs)
+        for (int k = 0; k < AI_NUM_CUTS; ++k) res_costs[i * AI_NUM_CUTS + k] = INFINITY;
     }
     return;
   }
@@ -1660,6 +1661,7 @@ __global__ __launch_bounds__(AI_BLOCK) void fk_sweep_final(const SegRec* __restr
         v[q] = a;
       }
       const double cost = __dadd_rn(__ddiv_rn(v[0], v[1]), __ddiv_rn(v[0], v[2]));
+      if (res_costs) res_costs[i * AI_NUM_CUTS + k] = cost;
       if (cost < best) {
         best = cost;
         kb = k;

@@ -1120,6 +1120,16 @@ __device__ __forceinline__ void mm_merge(MinMaxPart& r, const MinMaxPart& q) {
   }
 }
 
+// np.allclose(mn, mx) and thr[k] = np.linspace(mn, mx, 10, endpoint=False)[k] (normalized_cut.py:27): k * step + mn with TWO roundings,
+// as numpy forms it.  HIP's __dmul_rn / __dadd_rn are plain * and +, which the default -ffp-contract=fast fuses into one fma: up to
+// 1 ulp off numpy's thresholds (tests/test_gpu_flow_values.py compares them bit for bit).  No contraction in this function.
+__device__ __forceinline__ int32_t mm_thresholds(double mn, double mx, double* __restrict__ thr) {
+#pragma clang fp contract(off)
+  const double step = (mx - mn) / 10.0;
+  for (int k = 0; k < AI_NUM_CUTS; ++k) thr[k] = (double)k * step + mn;
+  return (fabs(mn - mx) <= 1e-8 + 1e-5 * fabs(mx)) ? 1 : 0;
+}
+
 __global__ __launch_bounds__(AI_BLOCK) void k_minmax(const Task* __restrict__ ctasks, const int32_t* __restrict__ mode,
                                                      const double* __restrict__ ev, const int32_t* __restrict__ orig,
                                                      MinMaxPart* __restrict__ part) {
@@ -1188,9 +1198,7 @@ __global__ void k_minmax_final(const int32_t* __restrict__ ctask0, const int32_t
   const double mn = (sc > 0.0) ? r.mn * sc : r.mx * sc;
   const double mx = (sc > 0.0) ? r.mx * sc : r.mn * sc;
   scale[s] = sc;
-  nosplit[s] = (fabs(mn - mx) <= 1e-8 + 1e-5 * fabs(mx)) ? 1 : 0;
-  const double step = __ddiv_rn(__dsub_rn(mx, mn), 10.0);
-  for (int k = 0; k < AI_NUM_CUTS; ++k) thr[s * AI_NUM_CUTS + k] = __dadd_rn(__dmul_rn((double)k, step), mn);
+  nosplit[s] = mm_thresholds(mn, mx, thr + s * AI_NUM_CUTS);
 }
 
 // bin_i = number of thresholds strictly below ev_i: mask_k(i) = (ev_i > t_k) = (k < bin_i)

@@ -201,7 +201,9 @@ int ai_ncut_batch(ai_ctx* ctx, const ai_csr* const* graphs, int32_t count, const
                   int32_t* n_groups, ai_ncut_stats* stats);
 
 /*
- * Building blocks exposed for parity tests (top-level call of the recursion only).
+ * Building blocks exposed for parity tests (top-level call of the recursion only).  These run the
+ * legacy Solver kernels (k_lz_* / k_sweep), NOT the ai_ncut / ai_ncut_batch path: the values of the
+ * path that ships are pinned per segment by the test-only dump (tests/test_gpu_flow_values.py).
  * ai_fiedler: eigenpair of the 2nd-smallest eigenvalue of L_sym = D^-1/2 (D - W) D^-1/2,
  *   W = w + I (normalized_cut.py:38-53); ev_out (n, host, original order) has unit norm and
  *   the library's sign convention (entry of largest magnitude positive).  The graph must be
