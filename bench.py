@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the NCuts hot path on MI355X (contract in the project brief, section (4)).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set-up, the untimed workspace calls and `--warmup` steps, the `--steps` timed
+steps, `--dump-outputs` if given, and one JSON line with `value` / `ms_per_step` and the run's description.  `--full` adds
+every other leg of the line after the timed steps (the host-input loop, the SpMV roofline in both regimes, the one-chunk
+latencies, the device copy rate and, at N = 1, the CPU baseline): the fields listed below under "Rank 0 prints ONE JSON line"
+beyond `value` are `--full` fields, except `config`, `self_checks`, `batch_ncut_ms` and `hbm_in_use_gb`.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks
 itself (one child process per GPU, started BEFORE this process imports torch or touches HIP; the
@@ -467,6 +473,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--in-flight", type=int, default=2, help="host threads (contexts) per GPU")
     ap.add_argument("--batch", type=int, default=12, help="chunks per batched call (their segments iterate in one pool)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the line's other legs: host inputs, SpMV roofline, one-chunk latencies, device copy rate, "
+                         "CPU baseline (N = 1); the --no-* and --cpu-50k switches below select among them")
     ap.add_argument("--cpu-50k", action="store_true", help="cpu_baseline: the single-process 50k-point oracle run on this host (~3 min) even when the pool leg took more than 200 s")
     ap.add_argument("--no-cpu-50k", action="store_true", help="cpu_baseline: skip the single-process 50k-point oracle run on this host")
     ap.add_argument("--batches", type=int, default=0, help="batched calls per GPU per step (default: one per host thread)")
@@ -545,7 +554,7 @@ def main():
     with ThreadPoolExecutor(max_workers=4) as gen:   # set-up only: ~2 s of NumPy per chunk
         for ch in gen.map(lambda c: synth.synthetic_chunk(N_POINTS, seed=c % (M * B), tarl=True), my_chunks):
             data.append((torch.from_numpy(ch["points"]).to(dev), torch.from_numpy(ch["tarl"]).to(dev)))
-            if not args.no_host_inputs and world == 1:   # the host-input leg is an N = 1 measurement
+            if args.full and not args.no_host_inputs and world == 1:   # the host-input leg is an N = 1 measurement
                 host.append((ch["points"], ch["tarl"]))
     torch.cuda.synchronize()
 
@@ -772,85 +781,87 @@ def main():
     nnz = res[0][3]
     stb = res[0][2]
 
-    # ---- the same loop with the inputs in pinned host memory (the library copies them on the context's stream)
-    host_steps, elapsed_host, hbm_host_leg, host_leg = 0, None, None, None
-    if host:
-        host_steps = args.steps   # as many as the resident leg: the first batch of each thread has nothing to hide its transfer behind
-        # the link alone: one batch's block, nothing else on the device
-        torch.cuda.synchronize()
-        t_a = time.perf_counter()
-        for _ in range(3):
-            stage_blocks[0].copy_(host_blocks[0], non_blocking=True)
+    # ---- --full only from here to the shutdown of the host threads: the line's other legs, each after the timed steps
+    if args.full:
+        # ---- the same loop with the inputs in pinned host memory (the library copies them on the context's stream)
+        host_steps, elapsed_host, hbm_host_leg, host_leg = 0, None, None, None
+        if host:
+            host_steps = args.steps   # as many as the resident leg: the first batch of each thread has nothing to hide its transfer behind
+            # the link alone: one batch's block, nothing else on the device
             torch.cuda.synchronize()
-        h2d_alone_gbps = 3 * host_blocks[0].numel() * 8 / (time.perf_counter() - t_a) / 1e9
-        run_steps(1, from_host=True)
-        h2d.update({"bytes": 0, "seconds": 0.0, "copies": 0, "wait_block_seconds": 0.0})
-        elapsed_host, _ = timed(host_steps, from_host=True)
-        host_leg = {
-            "gpu_numa_node": numa_node, "placement": numa_note, "loader_cpus": len(near_cpus) if near_cpus else None,
-            "h2d_gbps_alone": h2d_alone_gbps,                                   # one 1.9 GB copy at a time, idle device
-            "h2d_gbps_in_leg": h2d["bytes"] / max(h2d["seconds"], 1e-9) / 1e9,  # the same copies beside the kernels of the batches in flight
-            "loader_copy_frac": h2d["seconds"] / elapsed_host,                  # share of the leg's wall time the loader spent copying
-            "loader_wait_for_staging_block_frac": h2d["wait_block_seconds"] / elapsed_host,   # ... waiting for a free staging block (the kernels are the limit)
-            "copies": h2d["copies"], "bytes_per_copy": h2d["bytes"] // max(h2d["copies"], 1),
-        }
-        # the leg's device staging ring (K + 1 blocks of one batch's inputs) exists only for this leg
-        free_with_ring, _tot = torch.cuda.mem_get_info(dev)
-        hbm_host_leg = (_tot - free_with_ring) / 1e9
-        stage_blocks.clear()
-        torch.cuda.empty_cache()
+            t_a = time.perf_counter()
+            for _ in range(3):
+                stage_blocks[0].copy_(host_blocks[0], non_blocking=True)
+                torch.cuda.synchronize()
+            h2d_alone_gbps = 3 * host_blocks[0].numel() * 8 / (time.perf_counter() - t_a) / 1e9
+            run_steps(1, from_host=True)
+            h2d.update({"bytes": 0, "seconds": 0.0, "copies": 0, "wait_block_seconds": 0.0})
+            elapsed_host, _ = timed(host_steps, from_host=True)
+            host_leg = {
+                "gpu_numa_node": numa_node, "placement": numa_note, "loader_cpus": len(near_cpus) if near_cpus else None,
+                "h2d_gbps_alone": h2d_alone_gbps,                                   # one 1.9 GB copy at a time, idle device
+                "h2d_gbps_in_leg": h2d["bytes"] / max(h2d["seconds"], 1e-9) / 1e9,  # the same copies beside the kernels of the batches in flight
+                "loader_copy_frac": h2d["seconds"] / elapsed_host,                  # share of the leg's wall time the loader spent copying
+                "loader_wait_for_staging_block_frac": h2d["wait_block_seconds"] / elapsed_host,   # ... waiting for a free staging block (the kernels are the limit)
+                "copies": h2d["copies"], "bytes_per_copy": h2d["bytes"] // max(h2d["copies"], 1),
+            }
+            # the leg's device staging ring (K + 1 blocks of one batch's inputs) exists only for this leg
+            free_with_ring, _tot = torch.cuda.mem_get_info(dev)
+            hbm_host_leg = (_tot - free_with_ring) / 1e9
+            stage_blocks.clear()
+            torch.cuda.empty_cache()
 
-    # ---- roofline of the SpMV kernel, overlapped regime: the K host threads each run one batched call with HIP
-    # start/stop events on every SpMV dispatch, in flight together exactly as in the timed region
-    t_ov0 = time.perf_counter()
-    res_ov, _ = run_steps(1, profile="clock")
-    t_ov = time.perf_counter() - t_ov0
-    ov = {"launches": 0, "bytes": 0.0, "ms": 0.0, "blocks": 0, "blocks_idle": 0}
-    for k in range(M):
-        s = res_ov[k][2]
-        ov["blocks"] += int(s.get("spmv_blocks", 0))
-        ov["blocks_idle"] += int(s.get("spmv_blocks_idle", 0))
-        ov["launches"] += int(s["lanczos_steps"])
-        ov["bytes"] += spmv_bytes(int(s["spmv_rows"]), int(s["spmv_nnz"]), int(s["lanczos_steps"]))
-        ov["ms"] += s["ms_spmv"]
+        # ---- roofline of the SpMV kernel, overlapped regime: the K host threads each run one batched call with HIP
+        # start/stop events on every SpMV dispatch, in flight together exactly as in the timed region
+        t_ov0 = time.perf_counter()
+        res_ov, _ = run_steps(1, profile="clock")
+        t_ov = time.perf_counter() - t_ov0
+        ov = {"launches": 0, "bytes": 0.0, "ms": 0.0, "blocks": 0, "blocks_idle": 0}
+        for k in range(M):
+            s = res_ov[k][2]
+            ov["blocks"] += int(s.get("spmv_blocks", 0))
+            ov["blocks_idle"] += int(s.get("spmv_blocks_idle", 0))
+            ov["launches"] += int(s["lanczos_steps"])
+            ov["bytes"] += spmv_bytes(int(s["spmv_rows"]), int(s["spmv_nnz"]), int(s["lanczos_steps"]))
+            ov["ms"] += s["ms_spmv"]
 
-    # ---- one chunk alone (latency and per-chunk counters), then the solo regime: ONE batched call alone on the device
-    one_batch(0, only_first=True)
-    t1 = time.perf_counter()
-    for _ in range(3):
-        labs1, ngs1, st, _ = one_batch(0, only_first=True)
-    latency_ms = 1e3 * (time.perf_counter() - t1) / 3
-    ng = ngs1[0]
-    # the same for every chunk of the step (the seed-0 chunk above is one of the most expensive of the 24): affinity build +
-    # normalized cut of one chunk alone, once each after a warm-up call
-    lat_all, steps_all = [], []
-    for i in range(0 if args.no_latency_all else M * B):
-        for rep in range(2):
-            p_, f_ = data[i]
-            t1 = time.perf_counter()
-            g_ = api.build_affinity(p_, f_, alpha=CFG["alpha"], theta=CFG["theta"], gamma=CFG["gamma"], ctx=ctxs[0])
-            _, _, st_i = api.ncuts_labels(g_, N_POINTS, CFG["T"])
-            g_.free()
-            dt_i = 1e3 * (time.perf_counter() - t1)
-        lat_all.append(dt_i)
-        steps_all.append(int(st_i["lanczos_steps"]))
-    _, _, stp, _ = one_batch(0, profile="clock")
-    # a plain device-to-device copy on the same box (quote the roofline against a measured stream number too):
-    # 1 GiB read + 1 GiB written per repeat, alone on the device
-    src = torch.empty(1 << 27, dtype=torch.float64, device=dev).fill_(1.0)
-    dst = torch.empty_like(src)
-    dst.copy_(src)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(10):
+        # ---- one chunk alone (latency and per-chunk counters), then the solo regime: ONE batched call alone on the device
+        one_batch(0, only_first=True)
+        t1 = time.perf_counter()
+        for _ in range(3):
+            labs1, ngs1, st, _ = one_batch(0, only_first=True)
+        latency_ms = 1e3 * (time.perf_counter() - t1) / 3
+        ng = ngs1[0]
+        # the same for every chunk of the step (the seed-0 chunk above is one of the most expensive of the 24): affinity build +
+        # normalized cut of one chunk alone, once each after a warm-up call
+        lat_all, steps_all = [], []
+        for i in range(0 if args.no_latency_all else M * B):
+            for rep in range(2):
+                p_, f_ = data[i]
+                t1 = time.perf_counter()
+                g_ = api.build_affinity(p_, f_, alpha=CFG["alpha"], theta=CFG["theta"], gamma=CFG["gamma"], ctx=ctxs[0])
+                _, _, st_i = api.ncuts_labels(g_, N_POINTS, CFG["T"])
+                g_.free()
+                dt_i = 1e3 * (time.perf_counter() - t1)
+            lat_all.append(dt_i)
+            steps_all.append(int(st_i["lanczos_steps"]))
+        _, _, stp, _ = one_batch(0, profile="clock")
+        # a plain device-to-device copy on the same box (quote the roofline against a measured stream number too):
+        # 1 GiB read + 1 GiB written per repeat, alone on the device
+        src = torch.empty(1 << 27, dtype=torch.float64, device=dev).fill_(1.0)
+        dst = torch.empty_like(src)
         dst.copy_(src)
-    e1.record()
-    torch.cuda.synchronize()
-    copy_gbps = 10 * 2 * src.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    del src, dst
-    torch.cuda.empty_cache()
-    copy16_gbps = api.bench_copy(ctxs[0], 1 << 30, 10)   # the library's own float4 copy kernel (the guide measures 6.29 TB/s for one)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(10):
+            dst.copy_(src)
+        e1.record()
+        torch.cuda.synchronize()
+        copy_gbps = 10 * 2 * src.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+        del src, dst
+        torch.cuda.empty_cache()
+        copy16_gbps = api.bench_copy(ctxs[0], 1 << 30, 10)   # the library's own float4 copy kernel (the guide measures 6.29 TB/s for one)
     barrier()
     for _ in range(NB if NB else K):
         work.put(None)
@@ -866,13 +877,7 @@ def main():
     free_b, total_b = torch.cuda.mem_get_info(dev)
     if rank == 0:
         assert merged is not None and sorted(merged) == list(range(world * M * B)) and all(v.shape[0] == N_POINTS for v in merged.values())
-        launches = int(stp["lanczos_steps"])
-        b = spmv_bytes(int(stp["spmv_rows"]), int(stp["spmv_nnz"]), launches)
-        ach_solo = b / (stp["ms_spmv"] * 1e-3) / 1e9 if stp["ms_spmv"] > 0 else 0.0
-        ach_ov = ov["bytes"] / (ov["ms"] * 1e-3) / 1e9 if ov["ms"] > 0 else 0.0
         ms_step = 1e3 * elapsed / args.steps
-        ach_agg = ov["bytes"] / (ms_step * 1e-3) / 1e9   # every SpMV byte of one step / the step's wall time
-        traffic, traffic_src = pmc_traffic(B)
         out = {
             "metric": "chunks/sec (200k-pt TARL+Spatial NCuts chunk: affinity build + recursive normalized cut)",
             "value": world * M * B * args.steps / elapsed,
@@ -894,59 +899,69 @@ def main():
                                    f"alpha=1 theta=0.5 T=0.03; per GPU per step {M} batched calls of {B} chunks (one pool of iterating segments each) taken from a queue by {K} host threads" + (f"; {NB} builder thread(s) build the next batches' affinity graphs meanwhile" if NB else ""),
                        "n_points": N_POINTS, "nnz": int(nnz), "chunks_per_step": world * M * B, "threads_per_gpu": K, "builder_threads_per_gpu": NB, "chunks_per_batch": B, "batches_per_step": M,
                        "parallelism": f"chunk-dp{world}"},
-            "value_host_inputs": (world * M * B * host_steps / elapsed_host) if elapsed_host else None,
-            "host_inputs_ratio": (elapsed * host_steps / (elapsed_host * args.steps)) if elapsed_host else None,   # value_host_inputs / value
-            "host_inputs_note": "same loop, each batch's points + features in one pinned host block (159 MB per chunk), sent by a loader thread with one copy per batch into a ring of three device staging blocks, one batch ahead of the kernels"
-                                if elapsed_host else None,
-            "host_inputs": host_leg,   # where the pinned blocks and the loader thread ran, the link's rate alone and in the leg, what the loader waited for
+            "full": bool(args.full),   # whether the legs after the timed steps ran: the fields added below
             "hbm_in_use_gb": (total_b - free_b) / 1e9,   # inputs + K workspaces (arena, cached graph buffers) + torch
-            "hbm_in_use_host_inputs_gb": hbm_host_leg,   # the same + the host-input leg's staging ring
-            "single_chunk_latency_ms": latency_ms,   # the seed-0 chunk (per-chunk counters below are its)
-            "single_chunk_latency_ms_all": {"mean": sum(lat_all) / len(lat_all), "min": min(lat_all), "max": max(lat_all), "chunks": len(lat_all)} if lat_all else None,
-            "lanczos_steps_all": {"mean": sum(steps_all) / len(steps_all), "min": min(steps_all), "max": max(steps_all)} if steps_all else None,
             "batch_ncut_ms": stb["ms_total"],
-            "eigensolve_ms": st["ms_eigen"],
-            "ncut_ms": st["ms_total"],
-            "sweep_ms": st["ms_sweep"],
-            "rebuild_ms": st["ms_rebuild"],
-            "levels": int(st["levels"]),
-            "lanczos_solves": int(st["lanczos_solves"]),
-            "null_solves": int(st["null_solves"]),
-            "lanczos_steps": int(st["lanczos_steps"]),
-            "groups": int(ng),
-            "unconverged": int(st["unconverged"]),
-            "self_checks": dict(guard_counts),   # over every library call of this run (warm-up, timed, latency and profile passes)
-            "roofline": {
-                "kernel": "fk_spmv",
-                "bound": "hbm",
-                "achieved": ach_ov,
-                "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s",
-                "frac": ach_ov / HBM_PEAK_GBPS,
-                "frac_is": f"overlapped: {K} host threads in flight, as in the timed region",
-                "frac_overlapped": ach_ov / HBM_PEAK_GBPS,
-                "frac_solo": ach_solo / HBM_PEAK_GBPS,
-                "frac_aggregate": ach_agg / HBM_PEAK_GBPS,
-                "device_copy_gbps": max(copy_gbps, copy16_gbps),   # the box's best plain stream rate: 1 GiB device to device (read + write bytes), alone
-                "device_copy_gbps_torch": copy_gbps,             # torch's copy_
-                "device_copy_gbps_float4": copy16_gbps,          # hand-written 16-byte-per-lane copy (ai_bench_copy)
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "overlapped": {"launches": ov["launches"], "avg_launch_us": 1e3 * ov["ms"] / max(ov["launches"], 1),
-                               "bytes_per_launch_avg": ov["bytes"] / max(ov["launches"], 1), "achieved_gbps": ach_ov,
-                               "step_wall_ms_while_stamping": 1e3 * t_ov,
-                               # blocks dispatched for segments that had frozen since the task lists were written (they end after a record
-                               # and a flag load; the lists are rewritten at the next relist)
-                               "blocks": ov["blocks"], "blocks_idle": ov["blocks_idle"], "blocks_idle_frac": ov["blocks_idle"] / max(ov["blocks"], 1)},
-                "solo": {"launches": launches, "avg_launch_us": 1e3 * stp["ms_spmv"] / max(launches, 1),
-                         "bytes_per_launch_avg": b / max(launches, 1), "achieved_gbps": ach_solo},
-                "timer": "every SpMV launch stamps its own span (first block in .. last block out) on the device clock (wall_clock64)",
-                "aggregate_gbps": ach_agg,
-            },
+            "self_checks": dict(guard_counts),   # over every library call of this run (warm-up and timed steps; with --full also the legs after them)
         }
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only: the other ranks would sit in the final barrier
-            out["cpu_baseline"] = cpu_baseline(with_50k=False if args.no_cpu_50k else (True if args.cpu_50k else None),
-                                               gpu_labels=labs1[0], gpu_seed=my_chunks[0] % (M * B))
+        if args.full:
+            launches = int(stp["lanczos_steps"])
+            b = spmv_bytes(int(stp["spmv_rows"]), int(stp["spmv_nnz"]), launches)
+            ach_solo = b / (stp["ms_spmv"] * 1e-3) / 1e9 if stp["ms_spmv"] > 0 else 0.0
+            ach_ov = ov["bytes"] / (ov["ms"] * 1e-3) / 1e9 if ov["ms"] > 0 else 0.0
+            ach_agg = ov["bytes"] / (ms_step * 1e-3) / 1e9   # every SpMV byte of one step / the step's wall time
+            traffic, traffic_src = pmc_traffic(B)
+            out.update({
+                "value_host_inputs": (world * M * B * host_steps / elapsed_host) if elapsed_host else None,
+                "host_inputs_ratio": (elapsed * host_steps / (elapsed_host * args.steps)) if elapsed_host else None,   # value_host_inputs / value
+                "host_inputs_note": "same loop, each batch's points + features in one pinned host block (159 MB per chunk), sent by a loader thread with one copy per batch into a ring of three device staging blocks, one batch ahead of the kernels"
+                                    if elapsed_host else None,
+                "host_inputs": host_leg,   # where the pinned blocks and the loader thread ran, the link's rate alone and in the leg, what the loader waited for
+                "hbm_in_use_host_inputs_gb": hbm_host_leg,   # the same + the host-input leg's staging ring
+                "single_chunk_latency_ms": latency_ms,   # the seed-0 chunk (per-chunk counters below are its)
+                "single_chunk_latency_ms_all": {"mean": sum(lat_all) / len(lat_all), "min": min(lat_all), "max": max(lat_all), "chunks": len(lat_all)} if lat_all else None,
+                "lanczos_steps_all": {"mean": sum(steps_all) / len(steps_all), "min": min(steps_all), "max": max(steps_all)} if steps_all else None,
+                "eigensolve_ms": st["ms_eigen"],
+                "ncut_ms": st["ms_total"],
+                "sweep_ms": st["ms_sweep"],
+                "rebuild_ms": st["ms_rebuild"],
+                "levels": int(st["levels"]),
+                "lanczos_solves": int(st["lanczos_solves"]),
+                "null_solves": int(st["null_solves"]),
+                "lanczos_steps": int(st["lanczos_steps"]),
+                "groups": int(ng),
+                "unconverged": int(st["unconverged"]),
+                "roofline": {
+                    "kernel": "fk_spmv",
+                    "bound": "hbm",
+                    "achieved": ach_ov,
+                    "peak": HBM_PEAK_GBPS,
+                    "unit": "GB/s",
+                    "frac": ach_ov / HBM_PEAK_GBPS,
+                    "frac_is": f"overlapped: {K} host threads in flight, as in the timed region",
+                    "frac_overlapped": ach_ov / HBM_PEAK_GBPS,
+                    "frac_solo": ach_solo / HBM_PEAK_GBPS,
+                    "frac_aggregate": ach_agg / HBM_PEAK_GBPS,
+                    "device_copy_gbps": max(copy_gbps, copy16_gbps),   # the box's best plain stream rate: 1 GiB device to device (read + write bytes), alone
+                    "device_copy_gbps_torch": copy_gbps,             # torch's copy_
+                    "device_copy_gbps_float4": copy16_gbps,          # hand-written 16-byte-per-lane copy (ai_bench_copy)
+                    "traffic": traffic,
+                    "traffic_source": traffic_src,
+                    "overlapped": {"launches": ov["launches"], "avg_launch_us": 1e3 * ov["ms"] / max(ov["launches"], 1),
+                                   "bytes_per_launch_avg": ov["bytes"] / max(ov["launches"], 1), "achieved_gbps": ach_ov,
+                                   "step_wall_ms_while_stamping": 1e3 * t_ov,
+                                   # blocks dispatched for segments that had frozen since the task lists were written (they end after a record
+                                   # and a flag load; the lists are rewritten at the next relist)
+                                   "blocks": ov["blocks"], "blocks_idle": ov["blocks_idle"], "blocks_idle_frac": ov["blocks_idle"] / max(ov["blocks"], 1)},
+                    "solo": {"launches": launches, "avg_launch_us": 1e3 * stp["ms_spmv"] / max(launches, 1),
+                             "bytes_per_launch_avg": b / max(launches, 1), "achieved_gbps": ach_solo},
+                    "timer": "every SpMV launch stamps its own span (first block in .. last block out) on the device clock (wall_clock64)",
+                    "aggregate_gbps": ach_agg,
+                },
+            })
+            if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only: the other ranks would sit in the final barrier
+                out["cpu_baseline"] = cpu_baseline(with_50k=False if args.no_cpu_50k else (True if args.cpu_50k else None),
+                                                   gpu_labels=labs1[0], gpu_seed=my_chunks[0] % (M * B))
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

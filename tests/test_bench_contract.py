@@ -2,6 +2,8 @@
 import json
 import os
 
+import pytest
+
 from conftest import ROOT
 
 
@@ -11,7 +13,7 @@ def _newest_bench_line():
 
 
 def test_committed_bench_line_has_the_contract_fields():
-    """The newest `profiles/r*_bench_200k_line.json` (a `python bench.py` run on an MI355X box)."""
+    """The newest `profiles/r*_bench_200k_line.json` (a `python bench.py` run with every leg, today `--full`, on an MI355X box)."""
     with open(_newest_bench_line()) as f:
         line = json.loads(f.read().strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -33,6 +35,26 @@ def test_committed_bench_line_has_the_contract_fields():
         # since round 3: the pool is min(host cores, 128) workers and says which host the cached full-size run came from
         assert c["pool"]["cores"] == min(c["pool"]["host_cores_available"], 128) and "cpu_model" in c["cached_host"]
         assert r["kernel"] == "fk_spmv" and (r["traffic"] is None or r["traffic"] > 0)
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_prints_the_headline_only():
+    """`python bench.py` without `--full`: the timed steps and one line with the headline fields; the legs after the timed steps
+    (host inputs, roofline, one-chunk latencies, CPU baseline) are `--full` only."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["steps"] == 1 and line["warmup"] == 1
+    assert line["unit"] == "chunks/sec" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["metric"].startswith("chunks/sec") and line["value"] > 0
+    assert abs(line["value"] - line["config"]["chunks_per_step"] / (line["ms_per_step"] / 1e3)) < 1e-6 * line["value"]
+    for k in ("roofline", "cpu_baseline", "value_host_inputs", "single_chunk_latency_ms"):
+        assert k not in line, k
 
 
 def test_bench_launches_its_own_ranks_dry():

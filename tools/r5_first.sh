@@ -6,7 +6,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/gpu_suite.log 2>&1; r
 [ $rc -ne 0 ] && { tail -40 $O/gpu_suite.log; exit 1; }
 AI_NCUT_PHASES=1 timeout -k 10 300 python tools/probe_phases.py > $O/phases.log 2>&1; tail -8 $O/phases.log | cut -c1-900
 LINES_=30 tools/prof_phases.sh r5a
-timeout -k 10 600 python bench.py --steps 10 --no-cpu-baseline > $O/bench_line.json 2> $O/bench.err || { echo bench failed; tail -5 $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full --steps 10 --no-cpu-baseline > $O/bench_line.json 2> $O/bench.err || { echo bench failed; tail -5 $O/bench.err; exit 1; }
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r5a/bench_line.json").read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"; mkdir -p gpurun_out/sweep
 for tb in ${1:-2:12 3:8 3:12 4:6}; do
   t=${tb%%:*}; b=${tb##*:}
-  timeout -k 10 240 python bench.py --steps 6 --warmup 2 --in-flight $t --batch $b --no-cpu-baseline --no-host-inputs --no-latency-all \
+  timeout -k 10 240 python bench.py --full --steps 6 --warmup 2 --in-flight $t --batch $b --no-cpu-baseline --no-host-inputs --no-latency-all \
     > gpurun_out/sweep/t${t}_b${b}.json 2> gpurun_out/sweep/t${t}_b${b}.err || { echo "t=$t b=$b failed"; tail -3 gpurun_out/sweep/t${t}_b${b}.err; exit 1; }
   python - <<PY
 import json

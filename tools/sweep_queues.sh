@@ -2,7 +2,7 @@
 # bench.py under GPU_MAX_HW_QUEUES = ... (the runtime maps a process's streams onto that many hardware queues; default 4)
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"; mkdir -p gpurun_out/sweep
 for q in ${1:-4 6 8}; do
-  GPU_MAX_HW_QUEUES=$q timeout -k 10 240 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-host-inputs --no-latency-all \
+  GPU_MAX_HW_QUEUES=$q timeout -k 10 240 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-host-inputs --no-latency-all \
     > gpurun_out/sweep/q$q.json 2> gpurun_out/sweep/q$q.err || { echo "q=$q failed"; tail -3 gpurun_out/sweep/q$q.err; exit 1; }
   python - <<PY
 import json
