@@ -111,11 +111,15 @@ __global__ __launch_bounds__(AI_BLOCK) void k_cell_ranges(const int32_t* __restr
 }
 
 // cdist's euclidean kernel: sqrt((dx*dx + dy*dy) + dz*dz), every product and sum rounded on
-// its own (no fused multiply-add), so the radius test sees the reference's distance bit for bit
-// (ncuts_utils.py:60-61).
+// its own, so the radius test sees the reference's distance bit for bit (ncuts_utils.py:60-61).
+// HIP's __dmul_rn / __dadd_rn are plain * and + in headers compiled with the default
+// -ffp-contract=fast, which fused them into two v_fmac_f64: a pair within an ulp of the radius
+// could fall on the other side of it (tests/test_gpu_edges.py).  The pragma reaches only the
+// operators written here, so they are plain ones: three v_mul_f64, two v_add_f64.
 __device__ __forceinline__ double dist3(double ax, double ay, double az, double bx, double by, double bz) {
-  const double dx = __dsub_rn(ax, bx), dy = __dsub_rn(ay, by), dz = __dsub_rn(az, bz);
-  const double s = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+#pragma clang fp contract(off)
+  const double dx = ax - bx, dy = ay - by, dz = az - bz;
+  const double s = (dx * dx + dy * dy) + dz * dz;
   return __dsqrt_rn(s);
 }
 

@@ -18,6 +18,16 @@
 
 namespace {
 
+// The squared distance of both searches, in the order of nanoflann's L2_Adaptor (what open3d's KDTreeFlann runs) and of
+// cdist: (dx*dx + dy*dy) + dz*dz, every product and sum rounded on its own.  The default -ffp-contract=fast would fuse the
+// two adds into v_fmac_f64 and move a point within an ulp of the radius, or a near-tie, to the other side
+// (tests/test_gpu_edges.py).  No contraction in this function.
+__device__ __forceinline__ double sq_dist3(double x, double y, double z, double px, double py, double pz) {
+#pragma clang fp contract(off)
+  const double dx = x - px, dy = y - py, dz = z - pz;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
 struct PGrid {
   double minx, miny, minz, inv_cell;
   int nx, ny, nz;
@@ -87,9 +97,10 @@ __global__ __launch_bounds__(AI_BLOCK) void kp_gather(const double* __restrict__
   if (p == n - 1 || skey[p + 1] != c) cend[c] = (int32_t)(p + 1);
 }
 
-// 16 lanes per query point: mean of the float32 feature rows of all source points with
-// distance < radius (open3d's radius search is strict), accumulated in float64 like np.mean over
-// the float64 copy the reference holds.
+// 16 lanes per query point: mean of the float32 feature rows of all source points whose squared
+// distance (sq_dist3) is strictly below radius * radius rounded once -- nanoflann's radius search,
+// to which open3d passes the squared radius -- accumulated in float64 like np.mean over the float64
+// copy the reference holds.
 __global__ __launch_bounds__(AI_BLOCK) void kp_radius_mean(const double* __restrict__ q, int64_t nq, PGrid g, double radius,
                                                            const double* __restrict__ X, const double* __restrict__ Y,
                                                            const double* __restrict__ Z, const int32_t* __restrict__ order,
@@ -124,9 +135,7 @@ __global__ __launch_bounds__(AI_BLOCK) void kp_radius_mean(const double* __restr
         if (s < 0) continue;
         const int32_t e = cend[cc];
         for (int32_t p = s; p < e; ++p) {
-          const double ddx = x - X[p], ddy = y - Y[p], ddz = z - Z[p];
-          const double d2 = ddx * ddx + ddy * ddy + ddz * ddz;
-          if (d2 < r2) {
+          if (sq_dist3(x, y, z, X[p], Y[p], Z[p]) < r2) {
             const float* f = feat + (int64_t)order[p] * dim;
 #pragma unroll
             for (int k = 0; k < MAXK; ++k) {
@@ -147,7 +156,8 @@ __global__ __launch_bounds__(AI_BLOCK) void kp_radius_mean(const double* __restr
   if (t == 0 && count) count[i] = cnt;
 }
 
-// One thread per fine point: exact nearest source point by growing rings of cells; a ring r can
+// One thread per fine point: exact nearest source point (smallest sq_dist3, ties to the smaller
+// source index; distance = its correctly rounded sqrt) by growing rings of cells; a ring r can
 // only hold points at distance > (r - 1) * cell, so the search stops once best <= r * cell.
 __global__ __launch_bounds__(AI_BLOCK) void kp_nn1(const double* __restrict__ q, int64_t nq, PGrid g, double cell,
                                                    const double* __restrict__ X, const double* __restrict__ Y,
@@ -183,8 +193,7 @@ __global__ __launch_bounds__(AI_BLOCK) void kp_nn1(const double* __restrict__ q,
           if (s < 0) continue;
           const int32_t e = cend[cc];
           for (int32_t p = s; p < e; ++p) {
-            const double ddx = x - X[p], ddy = y - Y[p], ddz = z - Z[p];
-            const double d2 = ddx * ddx + ddy * ddy + ddz * ddz;
+            const double d2 = sq_dist3(x, y, z, X[p], Y[p], Z[p]);
             // ties: the smaller source index wins, so the answer does not depend on the cell order
             if (d2 < best || (d2 == best && order[p] < bi)) {
               best = d2;

@@ -225,6 +225,14 @@ __global__ __launch_bounds__(AI_BLOCK) void kq_gather(const double* __restrict__
   if (p == n - 1 || (uint32_t)(skey[p + 1] >> 32) != row) rend[row] = (int32_t)(p + 1);
 }
 
+// (dx*dx + dy*dy) + dz*dz with every step rounded, as the brute-force restatement and cKDTree's distances: without the
+// pragma the default -ffp-contract=fast fuses the adds into v_fmac_f64
+__device__ __forceinline__ double sq_dist3(double x, double y, double z, double px, double py, double pz) {
+#pragma clang fp contract(off)
+  const double dx = x - px, dy = y - py, dz = z - pz;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
 // keep the K smallest values seen in best[0..K-1] (ascending); compile-time indices only, so the list stays in registers
 template <int K>
 __device__ __forceinline__ void knn_insert(double (&best)[K], double d2) {
@@ -286,8 +294,7 @@ __global__ __launch_bounds__(AI_BLOCK) void kq_knn_avg(int64_t n, int32_t k, KGr
               b = m;
           }
           for (int32_t q = a; q < e && scx[q] <= hi; ++q) {
-            const double dx = x - X[q], dy = y - Y[q], dz = z - Z[q];
-            knn_insert<K>(best, dx * dx + dy * dy + dz * dz);
+            knn_insert<K>(best, sq_dist3(x, y, z, X[q], Y[q], Z[q]));
             ++seen;
           }
         }

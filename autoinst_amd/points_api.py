@@ -17,12 +17,15 @@ from .config import CHUNK_SIZE, MAJOR_VOXEL_SIZE, TARL_NORM
 from .ncuts_api import Context, default_context
 
 
-def tarl_pool(points_major, tarl_points, tarl_features, *, radius=MAJOR_VOXEL_SIZE / 2.0, ctx: Context | None = None):
+def tarl_pool(points_major, tarl_points, tarl_features, *, radius=MAJOR_VOXEL_SIZE / 2.0, return_count=False,
+              ctx: Context | None = None):
     """(N, F) float64: mean TARL feature within `radius` of every major-voxel point, zero row if none.
 
     ``tarl_points`` (M, 3) are the concatenated, already transformed and cropped scan points and
     ``tarl_features`` (M, F) their float32 features (``chunk_generation.py:218-241`` stay in Python:
-    they are dataset I/O).  The search is strict (< radius) like open3d's radius search.
+    they are dataset I/O).  A scan point is in the mean iff ``(dx*dx + dy*dy) + dz*dz``, each step
+    rounded, is strictly below ``radius * radius``: open3d's (nanoflann's) radius search.  With
+    ``return_count`` also the (N,) int32 number of scan points in each mean.
     """
     ctx = ctx or default_context()
     q = np.ascontiguousarray(points_major, dtype=np.float64)
@@ -31,13 +34,13 @@ def tarl_pool(points_major, tarl_points, tarl_features, *, radius=MAJOR_VOXEL_SI
     if q.ndim != 2 or q.shape[1] != 3 or s.ndim != 2 or s.shape[1] != 3 or f.ndim != 2 or f.shape[0] != s.shape[0]:
         raise ValueError("points must be (N, 3) / (M, 3) and features (M, F)")
     out = np.zeros((q.shape[0], f.shape[1]), dtype=np.float64)
+    cnt = np.zeros(q.shape[0], dtype=np.int32)
     if s.shape[0] == 0:
-        return out  # tarl_features stays all-zero in the reference too
-    cnt = np.empty(q.shape[0], dtype=np.int32)
+        return (out, cnt) if return_count else out  # tarl_features stays all-zero in the reference too
     _ffi.check(_ffi.load().ai_radius_mean_pool(ctx._h, q.ctypes.data, q.shape[0], s.ctypes.data, s.shape[0], f.ctypes.data,
                                                f.shape[1], float(radius), _ffi.AI_MEM_HOST, out.ctypes.data, cnt.ctypes.data),
                "ai_radius_mean_pool")
-    return out
+    return (out, cnt) if return_count else out
 
 
 def _transform_points(points, T):

@@ -160,12 +160,19 @@ def affinity_sparse(points, tarl=None, dino=None, *, alpha=1.0, theta=0.0, gamma
 
 
 def _rowwise_euclid(X, i, j, block=1 << 18):
-    """sqrt(sum((X[i]-X[j])**2)) like cdist's euclidean kernel, blocked over pairs."""
+    """sqrt(sum((X[i]-X[j])**2)) like cdist's euclidean kernel, blocked over pairs.
+
+    For 3-D points the squares are added in cdist's order, ``(dx*dx + dy*dy) + dz*dz``: einsum may pair them otherwise,
+    and one ulp decides the radius test of a pair at the radius (tests/test_edge_geometry.py)."""
     out = np.empty(i.shape[0], dtype=np.float64)
     for s in range(0, i.shape[0], block):
         e = min(s + block, i.shape[0])
         diff = X[i[s:e]] - X[j[s:e]]
-        out[s:e] = np.sqrt(np.einsum("ij,ij->i", diff, diff))
+        if diff.shape[1] == 3:
+            sq = diff * diff
+            out[s:e] = np.sqrt((sq[:, 0] + sq[:, 1]) + sq[:, 2])
+        else:
+            out[s:e] = np.sqrt(np.einsum("ij,ij->i", diff, diff))
     return out
 
 

@@ -20,9 +20,10 @@ def _scene(seed, n_major=4000, per_scan=30000, scans=4):
 def test_oracle_pooling_against_brute_force():
     major, src, feat = _scene(1, n_major=300, per_scan=2000, scans=2)
     got = points_ref.tarl_pool(major, src, feat, 0.175)
-    d = np.linalg.norm(major[:, None, :] - src[None, :, :], axis=2)
+    diff = major[:, None, :] - src[None, :, :]
+    d2 = (diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1]) + diff[..., 2] * diff[..., 2]
     for i in range(major.shape[0]):
-        idx = np.flatnonzero(d[i] < 0.175)
+        idx = np.flatnonzero(d2[i] < 0.175 * 0.175)   # the rule: the plain square below the squared radius
         exp = feat[idx].astype(np.float64).mean(0) if idx.size else np.zeros(96)
         assert np.abs(got[i] - exp).max() <= 1e-14
 
