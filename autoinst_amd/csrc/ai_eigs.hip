@@ -1,7 +1,8 @@
 // ai_eigs_smallest: the k smallest eigenpairs of L_sym (BASELINE.json configs[4], k = 64; the reference itself only asks
 // for k = 2, normalized_cut.py:49).  Every connected component contributes an explicit zero pair; the non-zero pairs of
-// a component come from Chebyshev-filtered subspace iteration (ai_chfsi.inc) or, for small graphs / few pairs, Lanczos
-// with full re-orthogonalisation (Solver::lanczos_fro).
+// a component come from Chebyshev-filtered subspace iteration (ai_chfsi.inc), from a dense host solve for components of at
+// most AI_EIGS_DENSE_ROWS rows, or, when a larger component gives a single pair, from Lanczos with full re-orthogonalisation
+// (Solver::lanczos_fro).
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -58,6 +59,65 @@ __global__ __launch_bounds__(AI_BLOCK) void k_scatter_rows(const double* __restr
   full[(size_t)i * n_full + orig[r]] = out[(size_t)i * n + r] * rn[i];
 }
 
+// Components of at most this many rows are solved densely on the host (dense_solve below).
+#ifndef AI_EIGS_DENSE_ROWS
+#define AI_EIGS_DENSE_ROWS 256
+#endif
+
+// theta 2 .. k1+1 of M = D^-1/2 (w + I) D^-1/2 of ONE small connected graph, on the host: the dense matrix of the very
+// entries the device solvers use (wm, sinv2), with 3 u1 u1^T subtracted so that the trivial pair moves to theta = -2, below
+// the whole spectrum: it can neither trade places with a lambda_2 of 1e-15 (two clusters joined by one faint edge) nor
+// mix into the eigenspace of theta = 0 that complete graphs and stars have when all n - 1 pairs are wanted.  The QL solver
+// of ai_dense_sym.h returns every eigenvalue with its full multiplicity, which single-vector Lanczos cannot: its Krylov
+// space holds one direction per eigenspace.  Vectors go to `out` (k1 rows, stride out_stride), thetas descending,
+// resids = ||M v - theta v|| recomputed from the sparse entries.
+int dense_solve(Solver& S, int k1, std::vector<double>& thetas, std::vector<double>& resids, double* out, size_t out_stride) {
+  const int n = S.segs[0].n;
+  const int64_t nnz = S.A->nnz;
+  hipStream_t st = S.st;
+  std::vector<int32_t> rp((size_t)n + 1), cl((size_t)std::max<int64_t>(nnz, 1));
+  std::vector<double> wm((size_t)std::max<int64_t>(nnz, 1)), s2(n), u1(n);
+  AI_HIP(hipMemcpyAsync(rp.data(), S.rowptr, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (nnz > 0) {
+    AI_HIP(hipMemcpyAsync(cl.data(), S.col, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AI_HIP(hipMemcpyAsync(wm.data(), S.wm.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  AI_HIP(hipMemcpyAsync(s2.data(), S.sinv2.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  AI_HIP(hipMemcpyAsync(u1.data(), S.u1.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  AI_HIP(hipStreamSynchronize(st));
+  std::vector<double> a((size_t)n * n, 0.0);
+  for (int i = 0; i < n; ++i) {
+    for (int p = rp[i]; p < rp[i + 1]; ++p) a[(size_t)i * n + cl[p]] += wm[p];
+    a[(size_t)i * n + i] += s2[i];
+  }
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j <= i; ++j) {
+      const double v = 0.5 * (a[(size_t)i * n + j] + a[(size_t)j * n + i]) - 3.0 * u1[i] * u1[j];
+      a[(size_t)i * n + j] = a[(size_t)j * n + i] = v;
+    }
+  std::vector<double> th, q;
+  if (!cf_eigh(a, n, th, q)) cf_jacobi(a, n, th, q);
+  thetas.assign(th.begin(), th.begin() + k1);
+  resids.assign(k1, 0.0);
+  std::vector<double> h((size_t)k1 * n);
+  for (int i = 0; i < k1; ++i) {
+    for (int r = 0; r < n; ++r) h[(size_t)i * n + r] = q[(size_t)r * n + i];
+    const double* v = &h[(size_t)i * n];
+    double s = 0.0;
+    for (int r = 0; r < n; ++r) {
+      double mv = s2[r] * v[r];
+      for (int p = rp[r]; p < rp[r + 1]; ++p) mv += wm[p] * v[cl[p]];
+      const double d = mv - thetas[i] * v[r];
+      s += d * d;
+    }
+    resids[i] = sqrt(s);
+  }
+  for (int i = 0; i < k1; ++i)
+    AI_HIP(hipMemcpyAsync(out + (size_t)i * out_stride, &h[(size_t)i * n], (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+  AI_HIP(hipStreamSynchronize(st));
+  return AI_OK;
+}
+
 // eigenpairs 2 .. k1+1 of ONE connected graph: k1 (lambda, unit vector) pairs, vectors scattered into
 // full-length rows of `vecs` (row stride n_full) at the positions csr->orig names
 // (`direct`: host rows of n_full doubles that receive the vectors instead of `vecs` -- the one-component case, no staging copy)
@@ -78,9 +138,15 @@ int eigs_connected(ai_ctx* ctx, const ai_csr* csr, const ai_ncut_opts* opts, int
   AI_TRY(out.alloc((size_t)k1 * n));
   std::vector<double> thetas, resids;
   int steps = 0;
+  // Single-vector Lanczos is exact for one pair only (any unit vector of a repeated lambda_2's eigenspace is an answer); for
+  // two or more it returns one copy of a repeated eigenvalue and then the next distinct one, and on a small component its
+  // Krylov space can run out before the pairs are formed.  So: dense up to AI_EIGS_DENSE_ROWS rows, Lanczos for one pair of
+  // a larger component, ChFSI for more.  AI_EIGS_LANCZOS=1 forces Lanczos (a debugging switch, valid on simple spectra only).
   static const int force_fro = getenv("AI_EIGS_LANCZOS") ? atoi(getenv("AI_EIGS_LANCZOS")) : 0;
-  if (!force_fro && n >= 1024 && k1 >= 3) {
-    // many pairs of a large graph: Chebyshev-filtered subspace iteration (block of 64 / 128 vectors)
+  if (!force_fro && n <= AI_EIGS_DENSE_ROWS) {
+    AI_TRY(dense_solve(S, k1, thetas, resids, out.p, (size_t)n));
+  } else if (!force_fro && k1 >= 2) {
+    // two or more pairs of a graph larger than the block: Chebyshev-filtered subspace iteration (block of 64 / 128 vectors)
     ChfsiStats cs;
     if (k1 <= 32)
       AI_TRY(chfsi_solve<1>(S, k1, S.opt.tol, thetas, resids, out.p, (size_t)n, &cs));
@@ -125,7 +191,9 @@ int eigs_connected(ai_ctx* ctx, const ai_csr* csr, const ai_ncut_opts* opts, int
     AI_HIP(hipStreamSynchronize(st));
   }
   for (int i = 0; i < got; ++i) {
-    lambdas.push_back(1.0 - thetas[i]);
+    // L_sym is positive semi-definite: a lambda_2 of O(1e-16) (two clusters joined by a faint edge) must not round to
+    // below the exact 0.0 of the zero pairs in front of it
+    lambdas.push_back(std::max(0.0, 1.0 - thetas[i]));
     if (max_resid) *max_resid = std::max(*max_resid, resids[i]);
   }
   if (steps_out) *steps_out = std::max(*steps_out, steps);
