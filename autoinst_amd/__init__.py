@@ -19,4 +19,7 @@ def __getattr__(name):
                 "chunk_and_downsample_point_clouds"):
         from . import prep_api as _p
         return getattr(_p, name)
+    if name in ("camera_features", "image_based_features_per_patch", "hidden_point_removal", "masks_to_image"):
+        from . import camera_api as _c
+        return getattr(_c, name)
     raise AttributeError(name)

@@ -24,3 +24,8 @@ CONFIG_SPATIAL = dict(name="spatial_1.0_t_0.075", alpha=1.0, theta=0.0, gamma=0.
 CONFIG_TARL_SPATIAL = dict(name="spatial_1.0_tarl_0.5_t_0.03", alpha=1.0, theta=0.5, gamma=0.0, beta=0.0, T=0.03)
 CONFIG_TARL_SPATIAL_DINO = dict(name="spatial_1.0_tarl_0.5_dino_0.1_t_0.005", alpha=1.0, theta=0.5, gamma=0.1, beta=0.0, T=0.005)
 CONFIG = CONFIG_TARL_SPATIAL  # config.py:87
+
+# the camera projection of the tri-modal configuration (image_utils.py:89-348, camera_api.py)
+HPR_RADIUS = 1000               # config.py:66  radius factor of the hidden point removal
+ADJACENT_FRAMES_CAM = (16, 13)  # config.py:70  scans before / after the chunk's first scan whose images are projected
+CAM_IDS = (0,)                  # config.py:72  cameras used, indices into ("cam2", "cam3")

@@ -239,3 +239,94 @@ def street_map(length: float = 120.0, seed: int = 0, *, step: float = 0.05, widt
     labels = {"seg_nonground": seg_ng, "instance_nonground": inst_ng, "seg_ground": seg_g, "instance_ground": inst_g}
     return {"nonground": nonground, "ground": ground, "labels": labels, "T_pcd": T_pcd, "positions": positions,
             "first_position": first_position, "indices": indices}
+
+
+def _rotation(axis, angle):
+    """Rotation matrix about a unit axis (Rodrigues)."""
+    a = np.asarray(axis, dtype=np.float64)
+    a = a / np.linalg.norm(a)
+    k = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.eye(3) + np.sin(angle) * k + (1.0 - np.cos(angle)) * (k @ k)
+
+
+def camera_rig(n_views: int = 29, seed: int = 0, *, length: float = 48.0, query_voxel: float = 0.17, fh: int = 27, fw: int = 88,
+               fdim: int = 384, image_hw=(376, 1241), n_masks: int = 12, keep_frac: float = 0.8):
+    """A seeded KITTI-like camera rig along `street_map`'s trajectory, enough to drive ``camera_api``.
+
+    The map is the street's two clouds (``pcd``, in the pcd frame); the chunk is the 25 m box around the street's middle
+    (``chunk_indices``, strict crop) and ``points`` its points averaged over ``query_voxel`` voxels (0.17 m: about 30 k points;
+    the pipeline's 0.35 m gives a quarter of that on this street).  The scans are numbered from 1 at one metre apart along the
+    centre line, the first views ~20 m before the chunk's centre, looking down the street; scan 0 has the identity pose (the
+    reference crops the map for its hidden point removal by ``get_pose(0)``).  The pcd-to-world transform is the street's
+    ``T_pcd``.  Per view: ``T_pcd2cam = (T_lidar2cam @ inv(pose)) @ T_pcd2world``.
+
+    ``T_lidar2cam`` maps x forward / z up to z forward / y down (with a small seeded tilt and KITTI's lever arm), ``K`` has
+    fx = fy = 718.856, cx = 607.1928, cy = 185.2157 and the image is 376 x 1241.  ``feature_maps`` (V, fh, fw, fdim) float32 with
+    fh / h and fw / w inexact (27 / 376, 88 / 1241), about 5 % all-zero and 3 % all-(-0.0) cells; ``sam_masks[v]``: rectangles
+    (row0, row1, col0, col1) of the view's SAM masks (``sam_images`` their ``masks_to_image`` labels, int32, 0 where no mask).
+    ``hpr_masks`` (V, len(pcd)) bool stands in for the hidden point removal: the points in front of the camera that project into
+    the image, a seeded ``keep_frac`` of them.
+    """
+    rng = np.random.default_rng(seed + 4242)
+    m = street_map(length, seed)
+    pcd = np.ascontiguousarray(np.concatenate([m["nonground"], m["ground"]]))
+    centre = np.array([length / 2.0, 0.0, 4.0])
+    lo, hi = centre - 12.5, centre + 12.5
+    chunk_indices = np.where(np.all(pcd > lo, axis=1) & np.all(pcd < hi, axis=1))[0]
+    chunk = pcd[chunk_indices]
+    key = np.floor((chunk - chunk.min(axis=0)) / query_voxel).astype(np.int64)
+    _, inv, cnt = np.unique(key, axis=0, return_inverse=True, return_counts=True)
+    inv = inv.reshape(-1)
+    points = np.stack([np.bincount(inv, weights=chunk[:, a]) for a in range(3)], 1) / cnt[:, None]
+    T_pcd2world = m["T_pcd"]
+    h, w = int(image_hw[0]), int(image_hw[1])
+    K = np.array([[718.856, 0.0, 607.1928], [0.0, 718.856, 185.2157], [0.0, 0.0, 1.0]])
+    T_lidar2cam = np.eye(4)
+    T_lidar2cam[:3, :3] = _rotation(rng.standard_normal(3), 0.01) @ np.array([[0.0, -1.0, 0.0], [0.0, 0.0, -1.0], [1.0, 0.0, 0.0]])
+    T_lidar2cam[:3, 3] = [0.06, -0.08, -0.27]
+    poses = {0: np.eye(4)}
+    cam_indices = list(range(1, n_views + 1))
+    x0 = centre[0] - 20.0
+    T_pcd2cam = np.empty((n_views, 4, 4))
+    for k, idx in enumerate(cam_indices):
+        local = np.eye(4)
+        local[:3, :3] = _rotation([0.0, 0.0, 1.0], 0.03 * rng.standard_normal())
+        local[:3, 3] = [x0 + k, 0.3 * rng.standard_normal(), 1.7]
+        poses[idx] = T_pcd2world @ local
+        T_pcd2cam[k] = (T_lidar2cam @ np.linalg.inv(poses[idx])) @ T_pcd2world
+    feature_maps = rng.standard_normal((n_views, fh, fw, fdim), dtype=np.float32)
+    cell = rng.random((n_views, fh, fw))
+    feature_maps[cell < 0.05] = 0.0
+    feature_maps[(cell >= 0.05) & (cell < 0.08)] = -0.0
+    sam_masks, sam_images = [], np.zeros((n_views, h, w), dtype=np.int32)
+    for v in range(n_views):
+        rects = []
+        for i in range(n_masks):
+            r0, c0 = int(rng.integers(0, h - 20)), int(rng.integers(0, w - 40))
+            r1, c1 = r0 + int(rng.integers(10, h // 2)), c0 + int(rng.integers(20, w // 3))
+            rects.append((r0, min(r1, h), c0, min(c1, w)))
+            sam_images[v, r0:r1, c0:c1] = i + 1
+        sam_masks.append(rects)
+    hpr_masks = np.zeros((n_views, pcd.shape[0]), dtype=bool)
+    x, y, z = pcd[:, 0], pcd[:, 1], pcd[:, 2]
+    for v in range(n_views):
+        T = T_pcd2cam[v]
+        cx, cy, cz = (T[r, 0] * x + T[r, 1] * y + T[r, 2] * z + T[r, 3] for r in range(3))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u, vv = (K[0, 0] * cx + K[0, 2] * cz) / cz, (K[1, 1] * cy + K[1, 2] * cz) / cz
+        hpr_masks[v] = (cz > 0.5) & (cz < 60.0) & (u > -1) & (u < w) & (vv > -1) & (vv < h) & (rng.random(pcd.shape[0]) < keep_frac)
+    return {"pcd": pcd, "chunk_indices": chunk_indices, "points": np.ascontiguousarray(points), "T_pcd2world": T_pcd2world,
+            "poses": poses, "cam_indices": cam_indices, "T_lidar2cam": T_lidar2cam, "K": K, "image_hw": (h, w),
+            "T_pcd2cam": T_pcd2cam, "feature_maps": feature_maps, "sam_masks": sam_masks, "sam_images": sam_images,
+            "hpr_masks": hpr_masks}
+
+
+def rig_sam_masks(rig, view: int):
+    """The SAM masks of one view of `camera_rig` as the dataset hands them out: a list of {"segmentation": bool (h, w)}."""
+    h, w = rig["image_hw"]
+    out = []
+    for r0, r1, c0, c1 in rig["sam_masks"][view]:
+        seg = np.zeros((h, w), dtype=bool)
+        seg[r0:r1, c0:c1] = True
+        out.append({"segmentation": seg})
+    return out

@@ -315,6 +315,30 @@ int ai_voxel_down_sample(ai_ctx* ctx, const double* xyz, int64_t n, double voxel
                          int64_t* n_out, int32_t* trace);
 
 /*
+ * The camera projection of the tri-modal configuration: image_based_features_per_patch (pipeline/utils/image/image_utils.py:
+ * 146-348, point_to_pixels.py:6-35) and dinov2_mean (:363-371) for every (query point i, view v) pair:
+ *   1. q and the visible points go to the camera frame: row r = ((T[r,0]*x + T[r,1]*y) + T[r,2]*z) + T[r,3], divided by row 3;
+ *   2. (i, v) is seen iff some cloud_xyz[vis_index[k]], vis_off[v] <= k < vis_off[v+1], has sqrt(squared distance) < max_dist in
+ *      the camera frame (squared distance (dx*dx + dy*dy) + dz*dz);
+ *   3. u' = (K00*x + K01*y) + K02*z (v', w' likewise), u = rint(u'/w'), v = rint(v'/w'); kept iff 0 <= u < img_w, 0 <= v < img_h
+ *      and w' > 0 in double: pixel_out[i, v] = (u, v), else (-1, -1);
+ *   4. sam_out[i, v] = sam_img[v][v_px][u_px] when kept and that label is not 0, else -1;
+ *   5. the feature cell of a kept pair is ((int)(fh / img_h * v_px), (int)(fw / img_w * u_px)); a cell outside the map is
+ *      AI_ERR_BAD_ARG (the reference raises IndexError);
+ *   6. feat_mean[i] = the float64 sum, in view order, of the cells' rows that hold an element != 0, divided by their number
+ *      feat_views[i] (a zero row when there is none).
+ * query_xyz (nq x 3), cloud_xyz (nc x 3), vis_index, feat (n_views x fh x fw x fdim float32), sam_img (n_views x img_h x img_w) and
+ * the outputs are host or device per mem_kind; vis_off (n_views + 1), T_pcd2cam (n_views x 16, row-major 4 x 4, last row
+ * 0 0 0 1) and K (9, row-major) are HOST arrays.  n_views <= 64.  pixel_out (nq x n_views x 2) may be NULL; sam_out (nq x n_views)
+ * is NULL iff sam_img is; feat_mean (nq x fdim) and feat_views (nq) are NULL iff feat is.
+ */
+int ai_camera_project(ai_ctx* ctx, const double* query_xyz, int64_t nq, const double* cloud_xyz, int64_t nc,
+                      const int32_t* vis_index, const int64_t* vis_off, int32_t n_views, const double* T_pcd2cam, const double* K,
+                      int32_t img_h, int32_t img_w, double max_dist, const float* feat, int32_t fh, int32_t fw, int32_t fdim,
+                      const int32_t* sam_img, int mem_kind, int32_t* pixel_out, int32_t* sam_out, double* feat_mean,
+                      int32_t* feat_views);
+
+/*
  * Timing hook for bench.py: runs `reps` fused Lanczos SpMV steps on the whole graph as
  * one segment and returns the average kernel time (HIP events on the context's stream)
  * plus the algorithmic byte count of one launch.
