@@ -929,8 +929,9 @@ extern "C" int ai_affinity_build_sam(ai_ctx* ctx, const double* xyz, int64_t n, 
                        (uint64_t)n * (uint64_t)std::max(has_t ? tarl_dim : 0, has_d ? dino_dim : 0) < ((uint64_t)1 << 33);  // staging offsets: 32 bits of 16-byte units
     if (tiled) {
       // LDS-tiled: every distinct neighbour's feature row is read once per 16-row tile
-      // 32-row tiles (512 threads) by default; AI_WEIGHTS_TILE=16 selects the 16-row form of rounds 2-4 (same bits: an entry's sum
-      // does not depend on the tile it is computed in)
+      // 16-row tiles (256 threads) by default; AI_WEIGHTS_TILE=32 selects the 32-row form (512 threads: built and measured, not
+      // shipped, see README.md).  Same bits: an entry's sum does not depend on the tile it is computed in
+      // (tests/test_gpu_affinity.py compares the two forms bit for bit)
       static const int tile16 = getenv("AI_WEIGHTS_TILE") ? atoi(getenv("AI_WEIGHTS_TILE")) != 32 : 1;
       if (tile16)
         hipLaunchKernelGGL((k_weights_lanes<256, 256, 32>), dim3((unsigned)((n + 15) / 16)), dim3(256), 0, st, (const int32_t*)A->rowptr,
