@@ -164,6 +164,10 @@ __global__ __launch_bounds__(AI_BLOCK) void km_common(const uint64_t* __restrict
   }
 }
 
+// The (value, tag) entries -- three per selected point -- are ranked by an int32 scan over ns + 1 positions, so ns + 1 must fit
+// in int32.  n_map, n_chunk < 2^29 do not ensure that: 3 * (2^29 - 1 + 2^29 - 1) > 2^31.
+#define KM_MAX_SCALARS 2147483646
+
 // :451-456  intersection = #points of instance id2 with min_bound <= p <= max_bound of instance id1
 #define KM_BOX_TILE 256
 __global__ __launch_bounds__(AI_BLOCK) void km_inside(const double* __restrict__ xyz, const int32_t* __restrict__ inst, int64_t n,
@@ -362,6 +366,12 @@ extern "C" int ai_merge_associate(ai_ctx* ctx, const double* map_xyz, const int3
   AI_HIP(hipMemcpyAsync(&sel[1], pos2.p + n_chunk, sizeof(int32_t), hipMemcpyDeviceToHost, st));
   AI_HIP(hipStreamSynchronize(st));
   const int64_t ns = 3 * ((int64_t)sel[0] + sel[1]);
+  if (ns > KM_MAX_SCALARS) {
+    ai_set_error("ai_merge_associate: %d cropped map points + %d chunk points of instances give %lld coordinate scalars, "
+                 "more than the %lld that int32 positions can index",
+                 sel[0], sel[1], (long long)ns, (long long)KM_MAX_SCALARS);
+    return AI_ERR_BAD_ARG;
+  }
   if (ns > 0) {
     DevBuf<uint64_t> val, val2, dval;
     DevBuf<uint32_t> tag, tag2, dtag;

@@ -1,7 +1,9 @@
 // Exclusive prefix sum over int32 (row counts -> row pointers, flags -> ranks).
-// Two launches for up to 8.4 M elements: tile scans + tile totals, then every block adds the sum of the totals in front of it
-// (which it forms itself: at most 4096 values).  Until round 4 the totals were scanned by a recursive call -- six launches per
-// scan with the two one-word blits of its single-tile case, 47 scans per 200k-point chunk.  Longer inputs recurse as before.
+// Two launches for up to SCAN_MAX_DIRECT_TILES tiles (n <= 8 388 608): tile scans + tile totals, then every block adds the sum of
+// the totals in front of it (which it forms itself: at most 4096 values).  Until round 4 the totals were scanned by a recursive
+// call -- six launches per scan with the two one-word blits of its single-tile case, 47 scans per 200k-point chunk.  Longer inputs
+// (n >= 8 388 609) still recurse: the tile totals are scanned in place by a call of their own (direct again up to 2^34 elements,
+// beyond every caller's limit) and k_scan_add adds them back, five launches in all.  tests/label_cases.py sits on every boundary.
 #include "ai_common.h"
 
 #define SCAN_ITEMS 8
@@ -109,14 +111,8 @@ int ai_exclusive_scan_i32(hipStream_t stream, const int32_t* in, int32_t* out, i
     AI_KERNEL_CHECK();
     return AI_OK;
   }
-  // sums[0..nt] <- exclusive scan of tile totals (sums[nt] = grand total)
-  if (nt == 1) {
-    // single tile: the total is sums[0] and the only offset is zero
-    AI_HIP(hipMemcpyAsync(sums + 1, sums, sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
-    AI_HIP(hipMemsetAsync(sums, 0, sizeof(int32_t), stream));
-  } else {
-    AI_TRY(ai_exclusive_scan_i32(stream, sums, sums, nt, tmp + nt + 1, nullptr));
-  }
+  // sums[0..nt] <- exclusive scan of the tile totals in place (sums[nt] = grand total); the next level's sums follow at tmp + nt + 1
+  AI_TRY(ai_exclusive_scan_i32(stream, sums, sums, nt, tmp + nt + 1, nullptr));
   hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nt), dim3(AI_BLOCK), 0, stream, out, n, sums);
   AI_KERNEL_CHECK();
   if (total_out) AI_HIP(hipMemcpyAsync(total_out, out + n, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
