@@ -16,7 +16,7 @@ def __getattr__(name):
         from . import labels_api as _l
         return getattr(_l, name)
     if name in ("box_select", "statistical_inlier_indices", "voxel_down_sample", "chunks_from_pointcloud",
-                "chunk_and_downsample_point_clouds"):
+                "chunk_and_downsample_point_clouds", "voxel_down_sample_nearest", "downsample_map"):
         from . import prep_api as _p
         return getattr(_p, name)
     if name in ("camera_features", "image_based_features_per_patch", "hidden_point_removal", "masks_to_image"):

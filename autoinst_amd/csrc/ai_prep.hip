@@ -24,6 +24,12 @@
 //                             voxel's points in input-index order divided by their count.  open3d's output order comes from
 //                             a hash map; ours is ascending (ix, iy, iz).  Stable radix sort by a 64-bit voxel key, then one
 //                             thread per voxel sums serially: bit-equal to an np.add.at restatement.
+//   ai_voxel_down_sample_nearest -- the minor-voxel map of load_and_downsample_point_clouds (dataset_utils.py:285-370): the same
+//                             means (the same kernels, bit for bit) plus, per voxel, the input point nearest to its mean -- the
+//                             point whose label the reference copies (:306-311).  Smallest (dx*dx + dy*dy) + dz*dz, ties to the
+//                             smaller input index (our rule, ai_nn1_project's: open3d's KD-tree defines none).  The search runs
+//                             on the sort that made the means: the sorted unique keys are the table of occupied voxels, and the
+//                             voxels iz - r .. iz + r of one (ix, iy) row are one key range, i.e. one run of sorted points.
 #include <climits>
 #include <cmath>
 
@@ -409,6 +415,120 @@ __global__ __launch_bounds__(AI_BLOCK) void kv_mean(const double* __restrict__ x
   out[v * 3 + 2] = sz / c;
 }
 
+// ----------------------------------------------------------------------------- nearest input point of every voxel mean
+
+// the sorted points' coordinates, contiguous per voxel run (kq_gather's layout), and the table of occupied voxels: ukey[v] = the
+// key of voxel v (ascending, as the voxels are)
+__global__ __launch_bounds__(AI_BLOCK) void kn_gather(const double* __restrict__ xyz, const int32_t* __restrict__ order,
+                                                      const uint64_t* __restrict__ skey, const int32_t* __restrict__ vid, int64_t n,
+                                                      double* __restrict__ X, double* __restrict__ Y, double* __restrict__ Z,
+                                                      uint64_t* __restrict__ ukey) {
+  const int64_t p = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (p >= n) return;
+  const int64_t o = order[p];
+  X[p] = xyz[o * 3];
+  Y[p] = xyz[o * 3 + 1];
+  Z[p] = xyz[o * 3 + 2];
+  if (vid[p + 1] != vid[p]) ukey[vid[p]] = skey[p];  // p is the head of its voxel's run
+}
+
+struct NGrid {
+  double vmin[3], size;
+  int sy, sz;      // key = ix << sy | iy << sz | iz, as VGrid
+  int nx, ny, nz;  // indices per axis that the key has room for (powers of two >= the occupied range)
+};
+
+// One thread per voxel v (in key order, so that a wave's voxels are neighbours): the input point nearest to the voxel's mean c.
+// Ring r is the shell of voxels at Chebyshev index distance r from v's own voxel.  In a row (ix + dx, iy + dy) on the shell's
+// faces (max(|dx|, |dy|) == r) the voxels iz - r .. iz + r are one key range; in an inner row the shell has the two voxels
+// iz - r and iz + r.  A key range is found by a binary search in ukey (for v's own row inside [v - r, v + r]: the row's voxels
+// are v's neighbours in the table) and is one run [start[a], start[b]) of the sorted points.
+// Stop rule (kp_nn1's, with the rounding counted): a point outside rings 0..r has, on some axis, a computed voxel index beyond
+// i - r .. i + r, so it lies beyond that face of the box of rings 0..r.  `lb` is the distance from c to the nearest such face,
+// less 8 ulps of the largest magnitude that enters the index and the face (the subtraction p - vmin, the division, i * size +
+// vmin), which covers the rounding of every one of them: strictly below the distance of every unvisited point.  Hence
+// sqrt(best) <= lb leaves no unvisited point that is nearer or tied.  In exact arithmetic ring 1 always ends the search (DESIGN.md
+// section 13); the loop does not rely on it.
+__global__ __launch_bounds__(AI_BLOCK) void kn_nearest(int64_t m, NGrid g, const double* __restrict__ cen,
+                                                       const uint64_t* __restrict__ ukey, const int32_t* __restrict__ start,
+                                                       const double* __restrict__ X, const double* __restrict__ Y,
+                                                       const double* __restrict__ Z, const int32_t* __restrict__ order,
+                                                       int32_t* __restrict__ nn_idx, double* __restrict__ nn_dist) {
+  const int64_t v = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (v >= m) return;
+  const double cx = cen[v * 3], cy = cen[v * 3 + 1], cz = cen[v * 3 + 2];
+  const uint64_t key = ukey[v];
+  const int64_t iz = (int64_t)(key & ((uint64_t)g.nz - 1));
+  const int64_t iy = (int64_t)((key >> g.sz) & ((uint64_t)g.ny - 1));
+  const int64_t ix = (int64_t)(key >> g.sy);
+  const double mag = fmax(fmax(fabs(g.vmin[0]) + (double)g.nx * g.size, fabs(g.vmin[1]) + (double)g.ny * g.size),
+                          fabs(g.vmin[2]) + (double)g.nz * g.size);
+  const double slack = 8.0 * 2.220446049250313e-16 * (mag + 2.0 * g.size);
+  double best = INFINITY;
+  int32_t bi = INT_MAX;
+  auto scan = [&](int32_t s, int32_t e) {
+    for (int32_t p = s; p < e; ++p) {
+      const double d2 = sq_dist3(cx, cy, cz, X[p], Y[p], Z[p]);
+      if (d2 <= best) {  // ties: the smaller input index wins, whichever voxel is visited first
+        const int32_t o = order[p];
+        if (d2 < best || o < bi) {
+          best = d2;
+          bi = o;
+        }
+      }
+    }
+  };
+  // the points of the voxels z0 .. z1 (clamped to the grid) of row (xx, yy); the range's first voxel is searched in [a, b)
+  auto scan_row = [&](int64_t xx, int64_t yy, int64_t z0, int64_t z1, int64_t a, int64_t b) {
+    z0 = max(z0, (int64_t)0);
+    z1 = min(z1, (int64_t)g.nz - 1);
+    if (z0 > z1) return;
+    const uint64_t row = ((uint64_t)xx << g.sy) | ((uint64_t)yy << g.sz);
+    const uint64_t klo = row | (uint64_t)z0, khi = row | (uint64_t)z1;
+    while (a < b) {  // first voxel with ukey >= klo
+      const int64_t h = (a + b) >> 1;
+      if (ukey[h] < klo)
+        a = h + 1;
+      else
+        b = h;
+    }
+    int64_t u = a;
+    while (u < m && ukey[u] <= khi) ++u;  // at most z1 - z0 + 1 steps
+    if (u > a) scan(start[a], start[u]);
+  };
+  scan(start[v], start[v + 1]);  // ring 0: the voxel's own members
+  const int64_t rmax = max(g.nx, max(g.ny, g.nz));
+  for (int64_t r = 0;; ++r) {
+    if (r > 0) {
+      for (int64_t dx = -r; dx <= r; ++dx) {
+        const int64_t xx = ix + dx;
+        if (xx < 0 || xx >= g.nx) continue;
+        for (int64_t dy = -r; dy <= r; ++dy) {
+          const int64_t yy = iy + dy;
+          if (yy < 0 || yy >= g.ny) continue;
+          const bool own = dx == 0 && dy == 0;
+          const int64_t a = own ? max(v - r, (int64_t)0) : 0, b = own ? min(v + r + 1, m) : m;
+          if (max(dx < 0 ? -dx : dx, dy < 0 ? -dy : dy) == r) {
+            scan_row(xx, yy, iz - r, iz + r, a, b);
+          } else {
+            scan_row(xx, yy, iz - r, iz - r, a, b);
+            scan_row(xx, yy, iz + r, iz + r, a, b);
+          }
+        }
+      }
+    }
+    if (r >= rmax) break;  // every voxel of the grid has been visited
+    const double rr = (double)r;
+    const double fx = fmin(cx - (g.vmin[0] + ((double)ix - rr) * g.size), (g.vmin[0] + ((double)ix + rr + 1.0) * g.size) - cx);
+    const double fy = fmin(cy - (g.vmin[1] + ((double)iy - rr) * g.size), (g.vmin[1] + ((double)iy + rr + 1.0) * g.size) - cy);
+    const double fz = fmin(cz - (g.vmin[2] + ((double)iz - rr) * g.size), (g.vmin[2] + ((double)iz + rr + 1.0) * g.size) - cz);
+    const double lb = fmin(fx, fmin(fy, fz)) - slack;
+    if (sqrt(best) * (1.0 + 4.0 * 2.220446049250313e-16) <= lb) break;
+  }
+  nn_idx[v] = bi;
+  if (nn_dist) nn_dist[v] = sqrt(best);
+}
+
 int bits_for(int64_t count) {  // bits that hold 0 .. count - 1
   int b = 0;
   while (b < 63 && ((int64_t)1 << b) < count) ++b;
@@ -676,6 +796,121 @@ extern "C" int ai_voxel_down_sample(ai_ctx* ctx, const double* xyz, int64_t n, d
   if (mem_kind != AI_MEM_DEVICE) {
     AI_HIP(hipMemcpyAsync(out_xyz, o, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     if (trace) AI_HIP(hipMemcpyAsync(trace, tr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  }
+  AI_HIP(hipStreamSynchronize(st));
+  *n_out = m;
+  return AI_OK;
+}
+
+extern "C" int ai_voxel_down_sample_nearest(ai_ctx* ctx, const double* xyz, int64_t n, double voxel_size, int mem_kind, double* out_xyz,
+                                            int64_t* n_out, int32_t* trace, int32_t* nearest_index, double* nearest_dist) {
+  if (!ctx || !n_out || (n > 0 && (!xyz || !out_xyz || !nearest_index)) || n < 0 || n >= ((int64_t)1 << 31) - AI_BLOCK) {
+    ai_set_error("ai_voxel_down_sample_nearest: bad argument");
+    return AI_ERR_BAD_ARG;
+  }
+  if (!(voxel_size > 0.0) || !std::isfinite(voxel_size)) {
+    ai_set_error("ai_voxel_down_sample_nearest: voxel_size <= 0");
+    return AI_ERR_BAD_ARG;
+  }
+  *n_out = 0;
+  if (n == 0) return AI_OK;
+  AI_HIP(hipSetDevice(ctx->device));
+  ArenaScope arena_scope(&ctx->arena);
+  hipStream_t st = ctx->stream;
+  DevBuf<double> own, d_out, X, Y, Z, d_dist;
+  DevBuf<uint64_t> key, skey;
+  DevBuf<int32_t> idx, order, vid, start, scan_tmp, d_trace, d_nn;
+  const double* dx;
+  AI_TRY(to_device(xyz, (size_t)n * 3, mem_kind, own, &dx, st));
+  double mn[3], mx[3];
+  AI_TRY(bounds(ctx, dx, n, mn, mx, "ai_voxel_down_sample_nearest"));
+  // the grid, the keys and the means are ai_voxel_down_sample's, step for step (and kernel for kernel)
+  VGrid g;
+  double vmin[3], span = 0.0;
+  int bits[3];
+  for (int a = 0; a < 3; ++a) {
+    vmin[a] = mn[a] - voxel_size * 0.5;
+    span = std::max(span, (mx[a] + voxel_size * 0.5) - vmin[a]);
+  }
+  if (voxel_size * (double)INT_MAX < span) {  // open3d: "voxel_size is too small."
+    ai_set_error("ai_voxel_down_sample_nearest: voxel_size is too small (a voxel index would leave the int range)");
+    return AI_ERR_BAD_ARG;
+  }
+  for (int a = 0; a < 3; ++a) bits[a] = bits_for((int64_t)floor((mx[a] - vmin[a]) / voxel_size) + 1);  // the largest index + 1
+  if (bits[0] + bits[1] + bits[2] > 64) {
+    ai_set_error("ai_voxel_down_sample_nearest: the voxel grid needs %d key bits (at most 64)", bits[0] + bits[1] + bits[2]);
+    return AI_ERR_BAD_ARG;
+  }
+  g.vminx = vmin[0];
+  g.vminy = vmin[1];
+  g.vminz = vmin[2];
+  g.size = voxel_size;
+  g.sz = bits[2];
+  g.sy = bits[1] + bits[2];
+  const unsigned gb = grid_for(n);
+  AI_TRY(key.alloc(n));
+  AI_TRY(skey.alloc(n));
+  AI_TRY(idx.alloc(n));
+  AI_TRY(order.alloc(n));
+  AI_TRY(vid.alloc(n + 1));
+  AI_TRY(start.alloc(n + 1));
+  AI_TRY(scan_tmp.alloc(ai_scan_tmp_elems(n)));
+  hipLaunchKernelGGL(kv_keys, dim3(gb), dim3(AI_BLOCK), 0, st, dx, n, g, key.p, idx.p);
+  AI_KERNEL_CHECK();
+  AI_TRY(sort_pairs(st, key.p, skey.p, idx.p, order.p, n, std::max(1, bits[0] + bits[1] + bits[2])));
+  hipLaunchKernelGGL(kv_heads, dim3(gb), dim3(AI_BLOCK), 0, st, (const uint64_t*)skey.p, n, vid.p);
+  AI_KERNEL_CHECK();
+  AI_TRY(ai_exclusive_scan_i32(st, vid.p, vid.p, n, scan_tmp.p));
+  hipLaunchKernelGGL(kv_starts, dim3(grid_for(n + 1)), dim3(AI_BLOCK), 0, st, (const int32_t*)vid.p, n, start.p);
+  AI_KERNEL_CHECK();
+  int32_t m = 0;
+  AI_HIP(hipMemcpyAsync(&m, vid.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  // the sorted coordinates and the voxel table do not need m: they run while the count comes back
+  AI_TRY(X.alloc(n));
+  AI_TRY(Y.alloc(n));
+  AI_TRY(Z.alloc(n));
+  uint64_t* ukey = key.p;  // the unsorted keys are dead after the sort: their buffer holds the voxel table
+  hipLaunchKernelGGL(kn_gather, dim3(gb), dim3(AI_BLOCK), 0, st, dx, (const int32_t*)order.p, (const uint64_t*)skey.p,
+                     (const int32_t*)vid.p, n, X.p, Y.p, Z.p, ukey);
+  AI_KERNEL_CHECK();
+  AI_HIP(hipStreamSynchronize(st));
+  double* o = out_xyz;
+  int32_t* tr = trace;
+  int32_t* ni = nearest_index;
+  double* nd = nearest_dist;
+  if (mem_kind != AI_MEM_DEVICE) {
+    AI_TRY(d_out.alloc((size_t)m * 3));
+    AI_TRY(d_nn.alloc(m));
+    o = d_out.p;
+    ni = d_nn.p;
+    if (trace) {
+      AI_TRY(d_trace.alloc(n));
+      tr = d_trace.p;
+    }
+    if (nearest_dist) {
+      AI_TRY(d_dist.alloc(m));
+      nd = d_dist.p;
+    }
+  }
+  hipLaunchKernelGGL(kv_mean, dim3(grid_for(m)), dim3(AI_BLOCK), 0, st, dx, (const int32_t*)order.p, (const int32_t*)start.p, (int64_t)m,
+                     o, tr);
+  AI_KERNEL_CHECK();
+  NGrid ng;
+  for (int a = 0; a < 3; ++a) ng.vmin[a] = vmin[a];
+  ng.size = voxel_size;
+  ng.sy = g.sy;
+  ng.sz = g.sz;
+  ng.nx = 1 << bits[0];  // bits[a] <= 31: an index fits the int range
+  ng.ny = 1 << bits[1];
+  ng.nz = 1 << bits[2];
+  hipLaunchKernelGGL(kn_nearest, dim3(grid_for(m)), dim3(AI_BLOCK), 0, st, (int64_t)m, ng, (const double*)o, (const uint64_t*)ukey,
+                     (const int32_t*)start.p, (const double*)X.p, (const double*)Y.p, (const double*)Z.p, (const int32_t*)order.p, ni, nd);
+  AI_KERNEL_CHECK();
+  if (mem_kind != AI_MEM_DEVICE) {
+    AI_HIP(hipMemcpyAsync(out_xyz, o, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    AI_HIP(hipMemcpyAsync(nearest_index, ni, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (trace) AI_HIP(hipMemcpyAsync(trace, tr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (nearest_dist) AI_HIP(hipMemcpyAsync(nearest_dist, nd, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   AI_HIP(hipStreamSynchronize(st));
   *n_out = m;

@@ -8,6 +8,9 @@
 * self-training sample: ``.npz`` with ``pts, ncut_labels, kitti_labels, cluster_labels, semantic``
   (``pipeline/dataset/dataset_utils.py:604-611``, read by
   ``self-training/mask_pls/datasets/pseudo_dataset.py:147-153``);
+* minor-voxel labels: ``kitti_labels_preprocessed<seq>_<idx>.npz`` with ``instance_nonground, instance_ground, seg_ground,
+  seg_nonground``, each an ``(m, 1)`` column (``dataset_utils.py:378-384`` saves lists of 1-element rows, ``:311``; read back by
+  ``load_downsampled_pcds``, ``:427-434``);
 * per-chunk ``.pcd``: binary PCD with ``x y z rgb`` float32 fields, the instance encoded as the point's
   colour (``point_cloud_utils.py:65-75`` via open3d's writer).
 """
@@ -45,6 +48,26 @@ def write_selftrain_npz(path, pts, ncut_labels, kitti_labels, semantic) -> None:
 def read_selftrain_npz(path) -> dict:
     z = np.load(path)
     return {k: z[k] for k in ("pts", "ncut_labels", "kitti_labels", "cluster_labels", "semantic")}
+
+
+KITTI_LABEL_KEYS = ("instance_nonground", "instance_ground", "seg_ground", "seg_nonground")   # dataset_utils.py:380-383
+
+
+def write_kitti_labels_preprocessed_npz(path, kitti_labels) -> None:
+    """The labels of the minor-voxel maps (`prep_api.downsample_map`'s third value) as the reference stores them: its four
+    keys, each an ``(m, 1)`` column."""
+    cols = {}
+    for k in KITTI_LABEL_KEYS:
+        a = kitti_labels[k]
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        cols[k] = a.reshape(-1, 1)
+    np.savez(path, **cols)
+
+
+def read_kitti_labels_preprocessed_npz(path) -> dict:
+    """The four ``(m, 1)`` label columns, as ``load_downsampled_pcds`` reads them (``dataset_utils.py:427-434``)."""
+    with np.load(path) as z:
+        return {k: z[k] for k in KITTI_LABEL_KEYS}
 
 
 def write_pcd_binary(path, points, colors) -> None:

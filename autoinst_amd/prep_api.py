@@ -16,9 +16,15 @@ called at ``run_pipeline.py:129``) on arrays instead of open3d clouds.
   voxel_size / 2``, voxel ``floor((p - vmin) / voxel_size)``, output point = sum of the voxel's points in input order / count.
   open3d's output order is that of a hash map and means nothing; ours is ascending ``(ix, iy, iz)``;
 * `chunks_from_pointcloud` / `chunk_and_downsample_point_clouds` -- the reference's two functions
-  (``chunk_generation.py:96-180``, ``dataset_utils.py:489-567``) with point arrays where the reference has open3d clouds.
+  (``chunk_generation.py:96-180``, ``dataset_utils.py:489-567``) with point arrays where the reference has open3d clouds;
+* `voxel_down_sample_nearest` / `downsample_map` -- one step earlier, ``load_and_downsample_point_clouds``
+  (``dataset_utils.py:201-384``, called at ``run_pipeline.py:110``): the aggregated raw clouds go to ``MINOR_VOXEL_SIZE`` voxels
+  and every minor point takes the label of its nearest RAW point (the four KD-tree loops of ``:299-370``).  Nearest = smallest
+  ``(dx*dx + dy*dy) + dz*dz``, ties to the smaller raw index: the tie rule is ours, open3d's KD-tree defines none.  Not
+  reproduced: the order of open3d's hash map (ours is ascending voxel order), open3d's choice among tied points, and the
+  coloured clouds of ``color_pcd_by_labels``, which the reference only uses as KD-tree carriers.
 
-All three kernels are HIP (``csrc/ai_prep.hip``); there is no CPU fallback.  Inputs are NumPy arrays or float64 torch tensors
+All kernels are HIP (``csrc/ai_prep.hip``); there is no CPU fallback.  Inputs are NumPy arrays or float64 torch tensors
 on the context's GPU; device inputs give device outputs, so map -> major chunks -> `ncuts_api.build_affinity` /
 `sharding.run_chunks` copies no points to the host (only counts come back).
 """
@@ -29,7 +35,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from .config import CHUNK_SIZE, MAJOR_VOXEL_SIZE, OVERLAP
+from .config import CHUNK_SIZE, MAJOR_VOXEL_SIZE, MINOR_VOXEL_SIZE, OVERLAP
 from .ncuts_api import Context, _is_device_tensor, default_context
 
 
@@ -133,6 +139,79 @@ def voxel_down_sample(points, voxel_size=MAJOR_VOXEL_SIZE, *, return_trace=False
                "ai_voxel_down_sample")
     res = out[:m.value]
     return (res, tr[:n]) if return_trace else res
+
+
+def voxel_down_sample_nearest(points, voxel_size=MINOR_VOXEL_SIZE, *, return_trace=False, return_dist=False,
+                              ctx: Context | None = None):
+    """`voxel_down_sample` plus, for every output point, the index of the input point nearest to it (int64): the point whose
+    label ``load_and_downsample_point_clouds`` copies (``dataset_utils.py:306-311``).  Smallest ``(dx*dx + dy*dy) + dz*dz``,
+    ties to the smaller input index.  Returns ``(points_out, nearest_index)``, then ``trace`` (int32, as `voxel_down_sample`)
+    with ``return_trace`` and the distances (float64) with ``return_dist``, in that order.  One sort serves both results."""
+    ctx = ctx or default_context()
+    pts = _points(points)
+    n = int(pts.shape[0])
+    ptr, mem, torch = _call_args(pts)
+    cap = max(n, 1)
+    if torch:
+        def new(shape, dtype):
+            return torch.empty(shape, dtype=dtype, device=pts.device)
+
+        def addr(a):
+            return C.c_void_p(a.data_ptr()) if a is not None else None
+        f64, i32 = torch.float64, torch.int32
+    else:
+        def new(shape, dtype):
+            return np.empty(shape, dtype=dtype)
+
+        def addr(a):
+            return a.ctypes.data if a is not None else None
+        f64, i32 = np.float64, np.int32
+    out, nn = new((cap, 3), f64), new(cap, i32)
+    tr = new(cap, i32) if return_trace else None
+    dist = new(cap, f64) if return_dist else None
+    m = C.c_int64(0)
+    _ffi.check(_ffi.load().ai_voxel_down_sample_nearest(ctx._h, ptr, n, float(voxel_size), mem, addr(out), C.byref(m), addr(tr),
+                                                        addr(nn), addr(dist)), "ai_voxel_down_sample_nearest")
+    res = [out[:m.value], nn[:m.value].long() if torch else nn[:m.value].astype(np.int64)]
+    if return_trace:
+        res.append(tr[:n])
+    if return_dist:
+        res.append(dist[:m.value])
+    return tuple(res)
+
+
+LABEL_KEYS = ("seg_ground", "seg_nonground", "instance_ground", "instance_nonground")   # dataset_utils.py:192-196
+
+
+def downsample_map(pcd_nonground, pcd_ground, labels, voxel_size=MINOR_VOXEL_SIZE, *, ctx: Context | None = None):
+    """``load_and_downsample_point_clouds`` (``dataset_utils.py:201-384``) on arrays: the two aggregated clouds go to
+    ``voxel_size`` voxels and every minor point takes the labels of its nearest raw point.  ``labels`` holds the reference's
+    ``seg_ground``, ``seg_nonground``, ``instance_ground``, ``instance_nonground`` (``kitti_labels_*.npz``, ``:186-197``), each
+    ``(n,)`` or ``(n, 1)`` of any integer dtype, host array or device tensor.  Returns ``(pcd_ground_minor,
+    pcd_nonground_minor, kitti_labels)`` -- the first three values of ``load_downsampled_pcds`` (``:417-453``) -- with
+    ``kitti_labels[key] = labels[key].reshape(-1)[nearest_index]``; it goes unchanged into
+    `chunk_and_downsample_point_clouds`.  Device clouds give device clouds, and device labels stay on the device."""
+    ctx = ctx or default_context()
+    missing = [k for k in LABEL_KEYS if k not in labels]
+    if missing:
+        raise ValueError(f"labels lacks {missing}")
+    clouds = {"ground": _points(pcd_ground, "pcd_ground"), "nonground": _points(pcd_nonground, "pcd_nonground")}
+    flat = {}
+    for k in LABEL_KEYS:
+        a = labels[k]
+        a = a.reshape(-1) if _is_device_tensor(a) else np.asarray(a).reshape(-1)
+        if a.shape[0] != clouds[k.split("_")[1]].shape[0]:
+            raise ValueError(f"labels[{k!r}] has {a.shape[0]} entries for {clouds[k.split('_')[1]].shape[0]} points")
+        integer = not (a.dtype.is_floating_point or a.dtype.is_complex) if _is_device_tensor(a) else a.dtype.kind in "iub"
+        if not integer:
+            raise ValueError(f"labels[{k!r}] must be an integer array")
+        flat[k] = a
+    minor, kitti_labels = {}, {}
+    for cloud, pts in clouds.items():
+        minor[cloud], nearest = voxel_down_sample_nearest(pts, voxel_size, ctx=ctx)
+        for kind in ("seg", "instance"):
+            kitti_labels[f"{kind}_{cloud}"] = _take(flat[f"{kind}_{cloud}"], nearest)
+    return minor["ground"], minor["nonground"], kitti_labels
 
 
 def chunk_centres(T_pcd, positions, first_position, indices, *, chunk_size=CHUNK_SIZE, overlap=OVERLAP):

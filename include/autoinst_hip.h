@@ -306,6 +306,14 @@ int ai_unique_points(ai_ctx* ctx, const double* xyz, int64_t n, int mem_kind, in
  *   order: ascending (ix, iy, iz) (open3d's is the order of a hash map).  out_xyz (capacity n x 3), trace (n, may be NULL: the
  *   output row of every input point); *n_out = number of voxels.  voxel_size <= 0, or a voxel index outside the int range
  *   (open3d's "voxel_size is too small"), is AI_ERR_BAD_ARG.
+ *
+ * ai_voxel_down_sample_nearest: the minor-voxel map of load_and_downsample_point_clouds (dataset_utils.py:285-370), i.e.
+ *   voxel_down_sample_and_trace(voxel_size, min_bound, max_bound) plus, per output point, the raw point whose label the reference's
+ *   KD-tree loops copy (:306-311, :324-328, :340-350, :362-367).  out_xyz, *n_out and trace are ai_voxel_down_sample's, bit for bit,
+ *   with the same errors.  nearest_index[v] (capacity n) = the index of the input point nearest to out_xyz[v]: the smallest
+ *   (dx*dx + dy*dy) + dz*dz (every step rounded, no contraction), ties to the smaller input index -- ai_nn1_project's rule.  The tie
+ *   rule is ours: open3d's KD-tree defines none (and open3d is not installed where this is tested).  nearest_dist[v] (may be NULL) =
+ *   the correctly rounded sqrt of that square.  n = 0 gives *n_out = 0; n < 2^31 - 256 as for ai_box_select.
  */
 int ai_box_select(ai_ctx* ctx, const double* xyz, int64_t n, const double* boxes, int32_t n_boxes, int mem_kind,
                   int64_t cap, int32_t* out_index, int64_t* box_offsets, int64_t* n_total);
@@ -313,6 +321,9 @@ int ai_statistical_inliers(ai_ctx* ctx, const double* xyz, int64_t n, int32_t nb
                            int mem_kind, int32_t* keep_index, int64_t* n_keep, double* avg_out, double* stats_out);
 int ai_voxel_down_sample(ai_ctx* ctx, const double* xyz, int64_t n, double voxel_size, int mem_kind, double* out_xyz,
                          int64_t* n_out, int32_t* trace);
+int ai_voxel_down_sample_nearest(ai_ctx* ctx, const double* xyz, int64_t n, double voxel_size, int mem_kind,
+                                 double* out_xyz, int64_t* n_out, int32_t* trace, int32_t* nearest_index,
+                                 double* nearest_dist);
 
 /*
  * The camera projection of the tri-modal configuration: image_based_features_per_patch (pipeline/utils/image/image_utils.py:
