@@ -1,5 +1,5 @@
 // Chebyshev-filtered subspace iteration for the k smallest non-trivial eigenpairs of L_sym of ONE connected graph
-// (BASELINE.json configs[4]: k = 64 on a ~1M-row graph).  Included by ai_eigs.hip after the Solver class.
+// (BASELINE.json configs[4]: k = 64 on a ~1M-row graph).  Included by ai_eigs.inc after the Solver class.
 //
 // The reference only ever asks for k = 2 (normalized_cut.py:49); for k = 64 on a million rows single-vector Lanczos
 // with full re-orthogonalisation needs > 4000 steps (the 64th eigenvalue is 1e-5 of the spectrum away from the 65th)

@@ -3,27 +3,6 @@
 // a component come from Chebyshev-filtered subspace iteration (ai_chfsi.inc), from a dense host solve for components of at
 // most AI_EIGS_DENSE_ROWS rows, or, when a larger component gives a single pair, from Lanczos with full re-orthogonalisation
 // (Solver::lanczos_fro).
-#include <math.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <chrono>
-#include <set>
-
-#include <hip/hip_ext.h>
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "ai_common.h"
-
-#include "ai_ncut_params.h"
-#include "ai_tridiag.h"
-
-namespace {
-#include "ai_ncut_kernels.inc"
-#include "ai_ncut_solver.inc"
-}  // namespace
-
 #include "ai_chfsi.inc"
 
 namespace {

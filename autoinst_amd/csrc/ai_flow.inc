@@ -1,6 +1,6 @@
 // Host side of the ASYNCHRONOUS FRONTIER of the recursive normalized cut (class Flow; kernels in ai_flow_kernels.inc).
 //
-// The lock-step driver (ncut_lockstep in ai_ncut.hip) processes one recursion depth at a time: a level lasts until
+// The lock-step driver (ncut_lockstep in ai_solver.hip, test-only build) processes one recursion depth at a time: a level lasts until
 // its slowest segment has converged, and the deep levels of a chunk run alone on the device.  Here every segment
 // advances on its own:
 //   * the POOL holds every connected segment that is iterating; one Lanczos step = two launches (fk_spmv, fk_update)

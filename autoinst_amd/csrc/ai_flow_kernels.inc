@@ -1,6 +1,6 @@
 // Device kernels of the ASYNCHRONOUS FRONTIER of the recursive normalized cut (included by ai_ncut.hip inside its
-// anonymous namespace, after ai_ncut_kernels.inc whose device helpers -- Task, uf_find / uf_unite, sturm_lt, MinMaxPart,
-// mm_merge, TaskEnc, the AI_ENC_* capacities -- are shared).
+// anonymous namespace; the device helpers it has in common with the level-synchronous Solver -- Task, uf_find / uf_unite,
+// sturm_lt, MinMaxPart, mm_merge, TaskEnc, the AI_ENC_* capacities -- come from ai_ncut_shared.h).
 //
 // Layout (DESIGN.md section 3): every row of the call lives at its position p in the FINAL ordering from the start;
 // a segment is the position range [g0, g0 + n) and its children are sub-ranges of it (mask side first,

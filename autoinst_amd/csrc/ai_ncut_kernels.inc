@@ -1,19 +1,11 @@
-// Device kernels of the recursive normalized cut (included by ai_ncut.hip and ai_eigs.hip inside an anonymous namespace).
+// Device kernels of the level-synchronous Solver (included by ai_solver.hip inside its anonymous namespace, after
+// ai_ncut_shared.h; the shipped frontier has its own kernels in ai_flow_kernels.inc and takes nothing from this file).
 // Sections: degrees / scaling, connected components, null-space vector (ai_fiedler on a disconnected graph), lock-step
 // Lanczos (fused SpMV, update, convergence check, Ritz vectors), full re-orthogonalisation, threshold sweep,
 // partition + CSR rebuild (binary Fiedler cuts and the split into connected components).
 
-// A task = one block's contiguous row range inside ONE segment: {lo, hi, segment, first task of its segment}.
-typedef int4 Task;
 // For coarse tasks: the segment's fine-task range [x, y) and coarse-task range [z, w).
 typedef int4 TaskRange;
-
-// fixed-order sum of part[t0..t1) by one block; every thread returns the same value
-__device__ __forceinline__ double ai_range_sum(const double* __restrict__ part, int t0, int t1, double* sm) {
-  double a = 0.0;
-  for (int t = t0 + threadIdx.x; t < t1; t += AI_BLOCK) a += part[t];
-  return ai_block_sum(a, sm);
-}
 
 // ----------------------------------------------------------------------------- degrees, scaling
 // deg_i = 1 + sum_j w_ij (W = w + I, normalized_cut.py:38,42); s_i = 1 / sqrt(deg_i) (:43)
@@ -99,37 +91,6 @@ __global__ __launch_bounds__(AI_BLOCK) void k_scale(const Task* __restrict__ tas
 }
 
 // ----------------------------------------------------------------------------- connected components
-// Union-find with the smaller root as representative, so a component's label is its first row
-// and labels do not depend on scheduling.  Plain loads may be stale inside a launch (a CU's L1 is
-// not refreshed by other CUs' stores); that is harmless here: every value ever stored in
-// parent[x] is an ancestor of x with a smaller-or-equal id, and hooking is decided by an
-// agent-scope compare-and-swap whose failure returns the up-to-date parent.
-__device__ __forceinline__ int32_t uf_find(int32_t* parent, int32_t x) {
-  int32_t p = parent[x];
-  while (p != x) {
-    const int32_t gp = parent[p];
-    if (gp != p) parent[x] = gp;  // path halving (benign race)
-    x = p;
-    p = gp;
-  }
-  return x;
-}
-__device__ __forceinline__ void uf_unite(int32_t* parent, int32_t a, int32_t b) {
-  for (int guard = 0; guard < (1 << 22); ++guard) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a == b) return;
-    if (a < b) {
-      const int32_t t = a;
-      a = b;
-      b = t;
-    }
-    const int32_t old = atomicCAS(&parent[a], a, b);  // hook the larger (apparent) root under the smaller id
-    if (old == a) return;
-    a = old;  // a was no longer a root: continue from its true parent
-  }
-}
-
 // rows of segments that need a fresh labelling: parent = smallest neighbour id <= row (no cycles:
 // strictly decreasing chains); rows of the other segments keep the labels carried over the split
 __global__ __launch_bounds__(AI_BLOCK) void k_cc_init(const Task* __restrict__ tasks, const int32_t* __restrict__ need_cc,
@@ -299,7 +260,7 @@ __global__ __launch_bounds__(AI_BLOCK) void k_lz_init(const Task* __restrict__ c
 // 16 lanes per row (neighbour counts ~30-40) read 64-B / 128-B runs of col / wm; each lane group
 // keeps AI_ROW_ILP rows in flight so that the dependent chain rowptr -> col -> gather is overlapped
 // four deep; gathers of R_j are served by L2 / MALL.
-template <int LPR, int ILP, bool NOGATHER = false>
+template <int LPR, int ILP>
 __device__ __forceinline__ void spmv_body(int t, const Task* __restrict__ ftasks, const int32_t* __restrict__ factive,
                                           const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                           const double* __restrict__ wm, const double* __restrict__ sinv2,
@@ -338,7 +299,7 @@ __device__ __forceinline__ void spmv_body(int t, const Task* __restrict__ ftasks
     }
 #pragma unroll
     for (int u = 0; u < ILP; ++u)
-      if (c[u] >= 0) sum[u] = fma(w[u], NOGATHER ? (double)c[u] : Rj[c[u]], sum[u]);
+      if (c[u] >= 0) sum[u] = fma(w[u], Rj[c[u]], sum[u]);
   }
   double acc = 0.0;
 #pragma unroll
@@ -357,14 +318,14 @@ __device__ __forceinline__ void spmv_body(int t, const Task* __restrict__ ftasks
   if (threadIdx.x == 0) pA[t] = tot;
 }
 
-template <int LPR, int ILP, bool NOGATHER = false>
+template <int LPR, int ILP>
 __global__ __launch_bounds__(AI_BLOCK) void k_lz_spmv_t(const Task* __restrict__ ftasks, const int32_t* __restrict__ factive, int ntask,
                                                       const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                       const double* __restrict__ wm, const double* __restrict__ sinv2,
                                                       const double* __restrict__ Rj, double* __restrict__ Z,
                                                       double* __restrict__ pA) {
   __shared__ double sm[AI_BLOCK / 64];
-  spmv_body<LPR, ILP, NOGATHER>(ai_xcd_task(blockIdx.x, ntask), ftasks, factive, rowptr, col, wm, sinv2, Rj, Z, pA, sm);
+  spmv_body<LPR, ILP>(ai_xcd_task(blockIdx.x, ntask), ftasks, factive, rowptr, col, wm, sinv2, Rj, Z, pA, sm);
 }
 
 // ---- staged gather (the default SpMV): the 8-byte gathers of R_j, not the streamed bytes, bound the
@@ -373,12 +334,7 @@ __global__ __launch_bounds__(AI_BLOCK) void k_lz_spmv_t(const Task* __restrict__
 // Lanczos task gets its sorted distinct-column list `ucol` and every entry a 16-bit index into it;
 // a step then gathers each distinct R_j value ONCE into LDS (coalesced runs) and the per-entry
 // gather becomes an LDS read.  Sums are formed in exactly the order of the plain kernel.
-#define AI_ENC_MAXNNZ 4096  // entries of a task the encoder sorts in LDS
-#define AI_ENC_XCAP 1024    // distinct columns of a task staged in LDS (8 KB)
 #define AI_SPMV_PF 4         // rounds of 16 entries per row whose loads are in flight before the barrier
-struct TaskEnc {
-  int32_t uoff, ucnt;  // slice of the ucol pool; ucnt < 0: not encoded, the task gathers from global memory
-};
 
 __global__ __launch_bounds__(AI_BLOCK) void k_lz_encode(const Task* __restrict__ ftasks, const int32_t* __restrict__ rowptr,
                                                         const int32_t* __restrict__ col, int32_t pool_cap,
@@ -565,30 +521,6 @@ __global__ __launch_bounds__(AI_BLOCK) void k_lz_spmv_q(const Task* __restrict__
   if (threadIdx.x == 0) pA[t] = tot;
 }
 
-// span[0] = earliest block start, span[1] = latest block end of one launch (profiling only)
-__global__ __launch_bounds__(AI_BLOCK) void k_ts_reduce(const unsigned long long* __restrict__ ts, int nblk, unsigned long long* __restrict__ span) {
-  __shared__ unsigned long long smn[AI_BLOCK], smx[AI_BLOCK];
-  unsigned long long mn = ~0ull, mx = 0ull;
-  for (int b = threadIdx.x; b < nblk; b += AI_BLOCK) {
-    mn = min(mn, ts[2 * b]);
-    mx = max(mx, ts[2 * b + 1]);
-  }
-  smn[threadIdx.x] = mn;
-  smx[threadIdx.x] = mx;
-  __syncthreads();
-  for (int o = AI_BLOCK / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      smn[threadIdx.x] = min(smn[threadIdx.x], smn[threadIdx.x + o]);
-      smx[threadIdx.x] = max(smx[threadIdx.x], smx[threadIdx.x + o]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    span[0] = smn[0];
-    span[1] = smx[0];
-  }
-}
-
 struct LzSeg {
   int32_t* frozen;      // [S]
   int32_t* m;           // [S] size of T at freeze
@@ -728,42 +660,6 @@ __global__ __launch_bounds__(AI_BLOCK) void k_lz_update(const Task* __restrict__
   update_body(blockIdx.x, ctasks, cranges, L, j, pA, pBcur, pBnext, u1, Z, Rj, Rjm1, Rnext, sm3);
 }
 
-// Number of eigenvalues of T_m (diag a[0..m), squared off-diagonals bb[1..m), both in LDS) that
-// are < x, by sign changes of the leading principal minors p_i = det(T_i - x I), rescaled by
-// powers of two.  The LDS reads do not depend on the recurrence, so they pipeline.
-__device__ __forceinline__ int sturm_lt(const double* a, const double* bb, int m, double x) {
-  // one wave per SIMD: the recurrence is bound by instruction issue, so magnitudes are looked at every
-  // 8 rows only (|a - x| + b^2 < 4: eight rows move them by < 2^16; the rescale leaves 200 decades)
-  double pm = 1.0, p = a[0] - x;
-  int cnt = (p < 0.0) ? 1 : 0;
-  for (int i0 = 1; i0 < m; i0 += 8) {
-    double av[8], bv[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const int i = min(i0 + t, m - 1);
-      av[t] = a[i];
-      bv[t] = bb[i];
-    }
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      if (i0 + t < m) {
-        double pn = (av[t] - x) * p - bv[t] * pm;
-        if (pn == 0.0) pn = (p > 0.0) ? -1e-300 : 1e-300;  // a zero takes the sign opposite to its predecessor
-        cnt += ((pn < 0.0) != (p < 0.0)) ? 1 : 0;
-        pm = p;
-        p = pn;
-      }
-    }
-    const double ap = fabs(p);
-    if (ap > 1e100 || ap < 1e-100) {
-      const double sc = (ap > 1e100) ? 0x1p-400 : 0x1p400;
-      p *= sc;
-      pm *= sc;
-    }
-  }
-  return cnt;
-}
-
 // b_m = ||R_m - g_m u1|| per running segment from the update kernel's partials (main stream: the
 // partials are overwritten two steps later, the check itself runs on the side stream)
 __global__ __launch_bounds__(64) void k_lz_bnew(const TaskRange* __restrict__ seg_range, const int32_t* __restrict__ mode,
@@ -790,7 +686,6 @@ __global__ __launch_bounds__(64) void k_lz_bnew(const TaskRange* __restrict__ se
 // reached the segment's dimension / the step cap.  slot[0] counts the segments still running; work[]
 // accumulates rows and stored entries the SpMV kernel processed since the last check.  Reads only
 // history entries [0, m), which later steps never touch.
-#define AI_CHECK_THREADS 256
 __global__ __launch_bounds__(AI_CHECK_THREADS) void k_lz_check(const int32_t* __restrict__ seg_start, const TaskRange* __restrict__ seg_range,
                                                                const int32_t* __restrict__ mode, LzSeg L, const double* __restrict__ bnew_in,
                                                                int m, double tol, int max_iter, int steps_since,
@@ -1103,33 +998,6 @@ __global__ __launch_bounds__(AI_BLOCK) void k_ritz_multi(const Task* __restrict_
 }
 
 // ----------------------------------------------------------------------------- threshold sweep
-struct MinMaxPart {
-  double mn, mx, sumsq, amax;
-  int32_t amax_id;   // original id of the entry of largest magnitude (smallest id on ties)
-  int32_t amax_neg;  // that entry is negative
-};
-
-__device__ __forceinline__ void mm_merge(MinMaxPart& r, const MinMaxPart& q) {
-  r.mn = fmin(r.mn, q.mn);
-  r.mx = fmax(r.mx, q.mx);
-  r.sumsq += q.sumsq;
-  if (q.amax > r.amax || (q.amax == r.amax && q.amax_id < r.amax_id)) {
-    r.amax = q.amax;
-    r.amax_id = q.amax_id;
-    r.amax_neg = q.amax_neg;
-  }
-}
-
-// np.allclose(mn, mx) and thr[k] = np.linspace(mn, mx, 10, endpoint=False)[k] (normalized_cut.py:27): k * step + mn with TWO roundings,
-// as numpy forms it.  HIP's __dmul_rn / __dadd_rn are plain * and +, which the default -ffp-contract=fast fuses into one fma: up to
-// 1 ulp off numpy's thresholds (tests/test_gpu_flow_values.py compares them bit for bit).  No contraction in this function.
-__device__ __forceinline__ int32_t mm_thresholds(double mn, double mx, double* __restrict__ thr) {
-#pragma clang fp contract(off)
-  const double step = (mx - mn) / 10.0;
-  for (int k = 0; k < AI_NUM_CUTS; ++k) thr[k] = (double)k * step + mn;
-  return (fabs(mn - mx) <= 1e-8 + 1e-5 * fabs(mx)) ? 1 : 0;
-}
-
 __global__ __launch_bounds__(AI_BLOCK) void k_minmax(const Task* __restrict__ ctasks, const int32_t* __restrict__ mode,
                                                      const double* __restrict__ ev, const int32_t* __restrict__ orig,
                                                      MinMaxPart* __restrict__ part) {
@@ -1303,7 +1171,6 @@ __global__ __launch_bounds__(AI_BLOCK) void k_sweep(const Task* __restrict__ fta
 // Per segment: ncut_k = cut_k / assocA_k + cut_k / assocB_k; first strictly smaller cost wins
 // (normalized_cut.py:29-32); split iff mcut < T (:56).  One block per segment: column c of the
 // 40 partial columns is summed by 6 threads over interleaved task stripes, then in stripe order.
-#define SWF_STRIPES 6
 __global__ __launch_bounds__(AI_BLOCK) void k_sweep_final(const int32_t* __restrict__ ftask0, const int32_t* __restrict__ nosplit,
                                                           const double* __restrict__ part, double T, double* __restrict__ costs,
                                                           int32_t* __restrict__ kstar, int32_t* __restrict__ split,
@@ -1574,12 +1441,6 @@ __global__ __launch_bounds__(AI_BLOCK) void k_lsym_apply(const int32_t* __restri
   if (l == 0) y[row] = x[row] - fma(sinv2[row], x[row], sum);
 }
 
-// dst[i] = src[i] + add (src == nullptr: dst[i] = i + add): concatenation of several CSR graphs
-__global__ __launch_bounds__(AI_BLOCK) void k_offset_copy(int32_t* __restrict__ dst, const int32_t* __restrict__ src, int64_t n,
-                                                          int32_t add) {
-  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  if (i < n) dst[i] = (src ? src[i] : (int32_t)i) + add;
-}
 __global__ __launch_bounds__(AI_BLOCK) void k_iota(int32_t* __restrict__ a, int32_t n) {
   const int i = blockIdx.x * AI_BLOCK + threadIdx.x;
   if (i < n) a[i] = i;

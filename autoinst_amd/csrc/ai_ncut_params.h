@@ -1,4 +1,4 @@
-// Tile shapes and capacities shared by the kernels and the host driver of the recursion (ai_ncut.hip, ai_eigs.hip).
+// Tile shapes and capacities shared by the kernels and the host drivers of the recursion (ai_ncut.hip, ai_solver.hip).
 #pragma once
 #ifndef AI_FINE_ROWS
 #define AI_FINE_ROWS 32      // rows per block in the 16-lanes-per-row kernels (2 rows in flight per lane group; 16 / 128 measured slower, 64: 20.6 vs 17.4 us per launch on a whole 200k graph, 111 vs 121 chunks/s with the quad kernel)

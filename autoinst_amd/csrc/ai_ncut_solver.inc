@@ -1,6 +1,6 @@
-// Host side of one frontier level: task lists, packed uploads, degrees / components / scaling, lock-step Lanczos,
-// Lanczos with full re-orthogonalisation, threshold sweep (class Solver).  Included by ai_ncut.hip and ai_eigs.hip
-// inside an anonymous namespace, after ai_ncut_kernels.inc.
+// Host side of one level of the level-synchronous recursion: task lists, packed uploads, degrees / components / scaling,
+// lock-step Lanczos, Lanczos with full re-orthogonalisation, threshold sweep (class Solver).  Included by ai_solver.hip
+// inside its anonymous namespace, after ai_ncut_kernels.inc.
 // ----------------------------------------------------------------------------- host: driver
 struct SegHost {
   int start, n, gstart;
@@ -8,11 +8,6 @@ struct SegHost {
   int need_cc;  // 0: component labels were carried over a cut between whole components
   int chunk;    // which chunk of a batched call the segment belongs to
 };
-
-static double now_ms() {
-  using namespace std::chrono;
-  return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 template <typename T>
 struct Ptr {  // a device pointer into a larger blob (same `.p` spelling as DevBuf)
@@ -417,14 +412,14 @@ class Solver {
 
   // e0 / e1 (optional): HIP events that receive this dispatch's own start / stop timestamps
   int spmv_variant = -1;
-  template <int LPR, int ILP, bool NOGATHER = false>
+  template <int LPR, int ILP>
   int launch_spmv_t(int j, hipEvent_t e0, hipEvent_t e1) {
     static_assert((AI_BLOCK / LPR) * ILP == AI_FINE_ROWS, "a block covers exactly one fine task");
     if (e0) {
-      hipExtLaunchKernelGGL((k_lz_spmv_t<LPR, ILP, NOGATHER>), dim3(lzf.n), dim3(AI_BLOCK), 0, st, e0, e1, 0, (const Task*)lzf.d.p, (const int32_t*)factive.p,
+      hipExtLaunchKernelGGL((k_lz_spmv_t<LPR, ILP>), dim3(lzf.n), dim3(AI_BLOCK), 0, st, e0, e1, 0, (const Task*)lzf.d.p, (const int32_t*)factive.p,
                             lzf.n, rowptr, col, (const double*)wm.p, (const double*)sinv2.p, (const double*)vec(j), Y.p, pA.p);
     } else {
-      hipLaunchKernelGGL((k_lz_spmv_t<LPR, ILP, NOGATHER>), dim3(lzf.n), dim3(AI_BLOCK), 0, st, (const Task*)lzf.d.p, (const int32_t*)factive.p, lzf.n,
+      hipLaunchKernelGGL((k_lz_spmv_t<LPR, ILP>), dim3(lzf.n), dim3(AI_BLOCK), 0, st, (const Task*)lzf.d.p, (const int32_t*)factive.p, lzf.n,
                          rowptr, col, (const double*)wm.p, (const double*)sinv2.p, (const double*)vec(j), Y.p, pA.p);
     }
     AI_KERNEL_CHECK();
@@ -435,11 +430,7 @@ class Solver {
       const char* v = getenv("AI_SPMV_VARIANT");
       spmv_variant = v ? atoi(v) : 0;
     }
-    switch (spmv_variant) {
-      case 9: return launch_spmv_t<16, AI_ROW_ILP, true>(j, e0, e1);  // timing only: no gather of R_j (wrong results)
-      case 1: return launch_spmv_t<16, AI_ROW_ILP>(j, e0, e1);  // plain gather from global memory
-      default: break;
-    }
+    if (spmv_variant == 1) return launch_spmv_t<16, AI_ROW_ILP>(j, e0, e1);  // plain gather from global memory
     if (!enc_ready) return launch_spmv_t<16, AI_ROW_ILP>(j, e0, e1);
     unsigned long long* ts = (clock_spmv && tblock.p) ? tblock.p : (unsigned long long*)nullptr;
 #define AI_SPMV_ARGS                                                                                                                 \
@@ -888,11 +879,6 @@ class Solver {
     return AI_OK;
   }
 };
-
-static bool eligible(int n, int64_t n_orig, double split_lim) {
-  // normalized_cut.py:39-40: W.shape[0] > 2 and len(labels) / (num_points_orig + 1e-8) > split_lim
-  return n > 2 && ((double)n / ((double)n_orig + 1e-8)) > split_lim;
-}
 
 
 void fill_opts(Solver& S, const ai_ncut_opts* opts) {

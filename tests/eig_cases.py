@@ -7,7 +7,7 @@ it cheaply; rings, tori, complete graphs and stars have it in closed form as wel
 
 Every fixture is a float64 ``scipy.sparse.csr_matrix`` built on the CPU (point-cloud graphs through
 ``ncuts_ref.affinity_sparse``, never the device).  The solver branch a (case, k) reaches is restated from ``eigs_connected``
-(``csrc/ai_eigs.hip``) in `branches`.
+(``csrc/ai_eigs.inc``) in `branches`.
 """
 from __future__ import annotations
 
