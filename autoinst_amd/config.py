@@ -28,4 +28,5 @@ CONFIG = CONFIG_TARL_SPATIAL  # config.py:87
 # the camera projection of the tri-modal configuration (image_utils.py:89-348, camera_api.py)
 HPR_RADIUS = 1000               # config.py:66  radius factor of the hidden point removal
 ADJACENT_FRAMES_CAM = (16, 13)  # config.py:70  scans before / after the chunk's first scan whose images are projected
+ADJACENT_FRAMES_TARL = (10, 10)  # config.py:71  scans before / after the chunk's centre scan whose TARL features are pooled
 CAM_IDS = (0,)                  # config.py:72  cameras used, indices into ("cam2", "cam3")

@@ -4,7 +4,10 @@
   (``pipeline/utils/point_cloud/chunk_generation.py:243-256``);
 * `nn1_reproject` -- ``kDTree_1NN_feature_reprojection``
   (``pipeline/utils/point_cloud/point_cloud_utils.py:144-174``).
-Both run as HIP kernels over a uniform cell list; there is no CPU fallback.
+* `tarl_pool_map` / `tarl_features_per_map` -- the same pooling for every chunk of a map in one device call
+  (``ai_scan_pool``, ``csrc/ai_scanpool.hip``): the pose transform, the crop to each chunk's box, the choice of each
+  chunk's scans and the radius mean (``chunk_generation.py:221-256``), with every scan read and uploaded once.
+All run as HIP kernels over cell lists; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -13,8 +16,8 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from .config import CHUNK_SIZE, MAJOR_VOXEL_SIZE, TARL_NORM
-from .ncuts_api import Context, default_context
+from .config import ADJACENT_FRAMES_TARL, CHUNK_SIZE, MAJOR_VOXEL_SIZE, NUM_TARL_FEATURES, TARL_NORM
+from .ncuts_api import Context, _is_device_tensor, default_context
 
 
 def tarl_pool(points_major, tarl_points, tarl_features, *, radius=MAJOR_VOXEL_SIZE / 2.0, return_count=False,
@@ -84,6 +87,179 @@ def tarl_features_per_patch(dataset, pcd, T_pcd, center_position, tarl_indices, 
         nrm = np.linalg.norm(out, axis=1)
         has = out.any(axis=1)
         out[has] /= nrm[has, None]
+    return out
+
+
+def _rows(a, cols, dtype, name, on_dev):
+    """One contiguous (n, cols) array (host) or tensor (device) of ``dtype``; ``cols`` None: any width."""
+    if on_dev:
+        import torch
+        want = torch.float64 if dtype == np.float64 else torch.float32
+        if not _is_device_tensor(a) or a.dtype != want or a.dim() != 2 or (cols is not None and a.shape[1] != cols):
+            raise ValueError(f"{name} on the device must be {want} (n, {cols or 'F'}) tensors")
+        return a.contiguous()
+    a = np.asarray(a)
+    if a.size == 0 and a.ndim != 2:
+        a = a.reshape(0, cols or 0)
+    if a.ndim != 2 or (cols is not None and a.shape[1] != cols):
+        raise ValueError(f"{name} must be (n, {cols or 'F'}) arrays")
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _concat(parts, cols, dtype, name, on_dev, device):
+    """(all rows, int64 offsets with len(parts) + 1 entries) of a list of per-segment (n_s, cols) arrays or tensors.  Segments
+    without rows only count in the offsets; with no row at all the result is (0, width of the first part, or 0)."""
+    if not isinstance(parts, (list, tuple)):
+        raise ValueError(f"{name}: a list of per-segment arrays, or one array together with its offsets, is expected")
+    seq = [_rows(a, cols, dtype, name, on_dev) for a in parts]
+    off = np.zeros(len(seq) + 1, dtype=np.int64)
+    np.cumsum([int(a.shape[0]) for a in seq], out=off[1:])
+    full = [a for a in seq if a.shape[0]]
+    if len({int(a.shape[1]) for a in full}) > 1:
+        raise ValueError(f"{name}: every segment must have the same width")
+    if not full:
+        width = int(seq[0].shape[1]) if seq else (cols or 0)
+        if on_dev:
+            import torch
+            return torch.zeros((0, width), dtype=torch.float64 if dtype == np.float64 else torch.float32, device=device), off
+        return np.zeros((0, width), dtype=dtype), off
+    if on_dev:
+        import torch
+        return torch.cat(full), off
+    return np.concatenate(full), off
+
+
+def _segmented(parts, offsets, cols, dtype, name, on_dev, device):
+    """`_concat` of a list, or the caller's own concatenated array with its offsets."""
+    if offsets is None:
+        return _concat(parts, cols, dtype, name, on_dev, device)
+    return _rows(parts, cols, dtype, name, on_dev), np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+
+
+def tarl_pool_map(scan_points, scan_features, T_scan2pcd, chunk_points, boxes, scan_windows, *, radius=MAJOR_VOXEL_SIZE / 2.0,
+                  return_count=False, scan_offsets=None, chunk_offsets=None, ctx: Context | None = None):
+    """The TARL matrix of every chunk of a map in one device call (``ai_scan_pool``): a list with one (N_c, F) float64 array
+    per chunk, what `tarl_pool` gives for the chunk's transformed and cropped scans.
+
+    ``scan_points`` / ``scan_features``: one (n_s, 3) float64 and one (n_s, F) float32 array per sampled scan, each scan in its
+    own sensor frame -- or the concatenated arrays with ``scan_offsets`` (S + 1).  ``T_scan2pcd``: S 4x4 transforms to the pcd
+    frame (last row 0 0 0 1), applied in the fixed order of `camera_api.transform_points`.  ``chunk_points``: one (N_c, 3)
+    array of major-voxel points per chunk -- or the concatenated array with ``chunk_offsets`` (C + 1).  ``boxes``: (C, 6) or
+    (C, 2, 3), lo and hi of each chunk's crop.  ``scan_windows``: (C, 2), chunk c takes the scans at positions
+    ``first <= s < last`` of the scan list.
+
+    Scan point p of scan s is in the mean of a point q of chunk c iff s is in c's window, the transformed p lies strictly
+    inside c's box, and ``(dx*dx + dy*dy) + dz*dz < radius * radius`` (`tarl_pool`'s test).  The members are summed in float64
+    in an order that depends on their coordinates alone, so a chunk's rows are bit-identical whichever other chunks or scans
+    the call holds.  With float64 / float32 torch tensors on the context's GPU the inputs are used in place and the outputs are
+    device tensors, which `ncuts_api.build_affinity` and `sharding.run_chunks` take as they are.  With ``return_count`` also
+    the list of (N_c,) int32 member counts.
+    """
+    ctx = ctx or default_context()
+    first = scan_points if scan_offsets is not None else next(iter(scan_points), None)
+    qfirst = chunk_points if chunk_offsets is not None else next(iter(chunk_points), None)
+    dev = _is_device_tensor(first) or (first is None and _is_device_tensor(qfirst))
+    device = (first if _is_device_tensor(first) else qfirst).device if dev else None
+    xyz, soff = _segmented(scan_points, scan_offsets, 3, np.float64, "scan_points", dev, device)
+    feat, foff = _segmented(scan_features, scan_offsets, None, np.float32, "scan_features", dev, device)
+    q, qoff = _segmented(chunk_points, chunk_offsets, 3, np.float64, "chunk_points", dev, device)
+    if not np.array_equal(soff, foff) or int(feat.shape[0]) != int(xyz.shape[0]):
+        raise ValueError("scan_features: one feature row per scan point expected")
+    dim = int(feat.shape[1])
+    if int(xyz.shape[0]) == 0 and dim == 0:
+        dim = NUM_TARL_FEATURES   # no scan at all, so no width either: the reference's tarl_features stay np.zeros((N, 96))
+    n_scans, n_chunks = soff.size - 1, qoff.size - 1
+    if n_scans < 0 or n_chunks < 0:
+        raise ValueError("offsets must hold at least one entry")
+    if int(xyz.shape[0]) != (int(soff[-1]) if n_scans >= 0 else 0) or int(q.shape[0]) != int(qoff[-1]):
+        raise ValueError("the last offset must be the number of rows")
+    T = np.ascontiguousarray(np.asarray(T_scan2pcd, dtype=np.float64).reshape(-1, 16))
+    b = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, 6))
+    w = np.asarray(scan_windows).reshape(-1, 2)
+    if T.shape[0] != n_scans or b.shape[0] != n_chunks or w.shape[0] != n_chunks:
+        raise ValueError(f"{n_scans} transforms, {n_chunks} boxes and {n_chunks} windows expected, got {T.shape[0]}, {b.shape[0]}, "
+                         f"{w.shape[0]}")
+    if w.size and (w.min() < -2 ** 31 or w.max() >= 2 ** 31):
+        raise ValueError("scan_windows do not fit int32")
+    w = np.ascontiguousarray(w.astype(np.int32))
+    nq = int(q.shape[0])
+    if dev:
+        import torch
+        out = torch.empty((nq, dim), dtype=torch.float64, device=device)
+        cnt = torch.empty((nq,), dtype=torch.int32, device=device)
+        # the concatenations above were queued on torch's current stream, and the library reads them on its own
+        torch.cuda.current_stream(device).synchronize()
+
+        def ptr(a):
+            return C.c_void_p(a.data_ptr()) if a.numel() else None
+        mem = _ffi.AI_MEM_DEVICE
+    else:
+        out = np.empty((nq, dim), dtype=np.float64)
+        cnt = np.empty((nq,), dtype=np.int32)
+
+        def ptr(a):
+            return a.ctypes.data if a.size else None
+        mem = _ffi.AI_MEM_HOST
+    _ffi.check(_ffi.load().ai_scan_pool(ctx._h, ptr(xyz), soff.ctypes.data, n_scans, T.ctypes.data, ptr(feat), dim, ptr(q),
+                                        qoff.ctypes.data, n_chunks, b.ctypes.data, w.ctypes.data, float(radius), mem, ptr(out),
+                                        ptr(cnt)), "ai_scan_pool")
+    rows = [out[qoff[c]:qoff[c + 1]] for c in range(n_chunks)]
+    if return_count:
+        return rows, [cnt[qoff[c]:qoff[c + 1]] for c in range(n_chunks)]
+    return rows
+
+
+def tarl_window(sampled_indices_global, center_id, adjacent_frames=ADJACENT_FRAMES_TARL):
+    """[first, last) positions in ``sampled_indices_global`` of the scans the reference pools for a chunk whose centre scan is
+    ``center_id``: the slice of ``get_indices_feature_reprojection`` (``chunk_generation.py:261-271``)."""
+    idx = list(sampled_indices_global)
+    i = idx.index(center_id)
+    return max(0, i - adjacent_frames[0]), max(0, min(len(idx), i + adjacent_frames[1]))
+
+
+def tarl_features_per_map(dataset, chunk_downsample_dict, T_pcd, sampled_indices_global, *, adjacent_frames=ADJACENT_FRAMES_TARL,
+                          chunk_size=CHUNK_SIZE, major_voxel_size=MAJOR_VOXEL_SIZE, tarl_norm=TARL_NORM,
+                          ctx: Context | None = None):
+    """The TARL matrices of all chunks of a map: the list of what ``ncuts_chunk`` (``ncuts_utils.py:40-49, 136-142``) computes
+    chunk by chunk with ``tarl_features_per_patch``, from one `tarl_pool_map` call.
+
+    ``chunk_downsample_dict`` needs ``center_ids``, ``center_positions`` and ``pcd_nonground_chunks_major_downsampling``
+    (arrays or objects with ``.points``).  Chunk c pools the scans of `tarl_window` around ``center_ids[c]``; every scan in the
+    union of the windows is read once (``get_tarl_features``, ``get_point_cloud``, ``get_pose``), with ``T = inv(T_pcd) @
+    pose`` applied in the fixed order of `camera_api.transform_points`.  ``ai_scan_pool`` takes affine transforms only, and a
+    floating-point inverse and product need not return the last row 0 0 0 1 exactly: a last row within rounding of it (64 ulps
+    of the largest entry of T) is set to it, anything further off raises ``ValueError`` here, naming the scan.
+    """
+    idx = list(sampled_indices_global)
+    centers = np.asarray(chunk_downsample_dict["center_positions"], dtype=np.float64).reshape(-1, 3)
+    chunks = []
+    for pc in chunk_downsample_dict["pcd_nonground_chunks_major_downsampling"]:
+        chunks.append(np.asarray(pc.points if hasattr(pc, "points") and not isinstance(pc, np.ndarray) else pc, dtype=np.float64))
+    wins = np.array([tarl_window(idx, cid, adjacent_frames) for cid in chunk_downsample_dict["center_ids"]],
+                    dtype=np.int64).reshape(-1, 2)
+    used = np.zeros(len(idx) + 1, dtype=np.int64)
+    for a, b in wins:
+        used[a:b] = 1
+    rank = np.concatenate([[0], np.cumsum(used)])   # position in the list of sampled scans -> position among the scans read
+    pts, feats, Ts = [], [], []
+    T_inv = np.linalg.inv(np.asarray(T_pcd, dtype=np.float64))
+    for pos in np.flatnonzero(used):
+        points_index = idx[pos]
+        feats.append(np.asarray(dataset.get_tarl_features(points_index), dtype=np.float32))
+        pts.append(np.asarray(dataset.get_point_cloud(points_index), dtype=np.float64))
+        T = T_inv @ np.asarray(dataset.get_pose(points_index), dtype=np.float64)                 # :229-231
+        if np.abs(T[3] - [0.0, 0.0, 0.0, 1.0]).max() > 64 * np.finfo(np.float64).eps * max(1.0, np.abs(T[:3]).max()):
+            raise ValueError(f"tarl_features_per_map: inv(T_pcd) @ pose of scan {points_index} is not affine (last row {T[3]})")
+        T[3] = [0.0, 0.0, 0.0, 1.0]
+        Ts.append(T)
+    half = 0.5 * np.asarray(chunk_size, dtype=np.float64)
+    boxes = np.concatenate([centers - half, centers + half], axis=1)                             # :219-220
+    out = tarl_pool_map(pts, feats, np.array(Ts).reshape(-1, 4, 4), chunks, boxes, rank[wins], radius=major_voxel_size / 2.0, ctx=ctx)
+    if tarl_norm:                                                                                # :253-254
+        for o in out:
+            nrm = np.linalg.norm(o, axis=1)
+            has = o.any(axis=1)
+            o[has] /= nrm[has, None]
     return out
 
 

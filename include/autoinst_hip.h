@@ -350,6 +350,37 @@ int ai_camera_project(ai_ctx* ctx, const double* query_xyz, int64_t nq, const do
                       int32_t* feat_views);
 
 /*
+ * The TARL scan features of every chunk of a map in one call: tarl_features_per_patch (pipeline/utils/point_cloud/
+ * chunk_generation.py:221-256) for all chunks at once.  scan_xyz holds all sampled scans, one after the
+ * other, each in its own sensor frame (scan s: rows scan_off[s] .. scan_off[s+1]); scan_feat their float32 features (M x dim);
+ * query_xyz all chunks' major-voxel points (chunk c: rows query_off[c] .. query_off[c+1]); boxes[c] = lo x, y, z, hi x, y, z;
+ * scan_win[c] = [first, last) positions in the scan list (the reference's slice of sampled_indices_global, :261-271).
+ *   R1 Transform.  A scan point goes to the pcd frame in a fixed order: row r = ((T[r,0]*x + T[r,1]*y) + T[r,2]*z) + T[r,3],
+ *      divided by row 3, every step rounded on its own (no contraction; not a BLAS product).  A last row of T other than
+ *      (0, 0, 0, 1) is AI_ERR_BAD_ARG.
+ *   R2 Membership.  Point p of scan s is in the mean of query i of chunk c iff scan_win[c][0] <= s < scan_win[c][1], the
+ *      transformed p is strictly inside box c on all three axes (lo < p < hi), and (dx*dx + dy*dy) + dz*dz, every step rounded,
+ *      is strictly below radius * radius rounded once (ai_radius_mean_pool's test).
+ *   R3 Mean.  out[i] = the float64 sum of the member rows (float32 widened) divided once by their number count_out[i] (may be
+ *      NULL); a zero row when there is no member.
+ *   R4 Order.  Members are summed in ascending order of their cell index (ix, iy, iz), then ascending position in scan_xyz.
+ *      The cell index is floor(coord * (1 / cell)), cell = radius * (1 + 1e-9), origin 0 and signed (the key stores it less a
+ *      bias): the order is a function of the coordinates alone.  Two calls are bit-identical, and so are a chunk's rows
+ *      whether it is pooled alone or with other chunks, with only its window's scans or with the whole map's.
+ *   R5 Limits and errors.  M = scan_off[n_scans] and Nq = query_off[n_chunks] < 2^31 - 256.  AI_ERR_BAD_ARG: dim < 1 or > 384;
+ *      radius <= 0 or not finite; a window outside [0, n_scans] or with first > last; an offset array that does not start at 0
+ *      or decreases; a non-finite coordinate, box bound or transform; a cell index that does not fit its key field
+ *      (|index| >= 2^30, or the boxes' index ranges need more than 30 key bits on an axis or 63 together).  Not errors: n_chunks == 0, a chunk
+ *      with no queries, an empty window, a scan with no points, M == 0; a chunk with no members gets zero rows and counts.
+ *      The arguments are checked in full whether or not there is a query (scan coordinates included).
+ * scan_xyz, scan_feat, query_xyz, out and count_out are host or device per mem_kind; every other array is a HOST array
+ * (T_scan2pcd: n_scans x 16 row-major; boxes: n_chunks x 6; scan_win: n_chunks x 2; the offsets: n + 1 entries).
+ */
+int ai_scan_pool(ai_ctx* ctx, const double* scan_xyz, const int64_t* scan_off, int32_t n_scans, const double* T_scan2pcd,
+                 const float* scan_feat, int32_t dim, const double* query_xyz, const int64_t* query_off, int32_t n_chunks,
+                 const double* boxes, const int32_t* scan_win, double radius, int mem_kind, double* out, int32_t* count_out);
+
+/*
  * Timing hook for bench.py: runs `reps` fused Lanczos SpMV steps on the whole graph as
  * one segment and returns the average kernel time (HIP events on the context's stream)
  * plus the algorithmic byte count of one launch.
