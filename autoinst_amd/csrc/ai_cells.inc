@@ -29,7 +29,9 @@ __global__ __launch_bounds__(AI_BLOCK) void kp_bounds(const double* __restrict__
   for (int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * AI_BLOCK)
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      const double v = xyz[i * 3 + a];
+      // fmin / fmax drop a NaN: a coordinate that is not finite goes in as +inf, so that build_cells' extent check sees it
+      const double c = xyz[i * 3 + a];
+      const double v = fabs(c) < INFINITY ? c : INFINITY;
       mn[a] = fmin(mn[a], v);
       mx[a] = fmax(mx[a], v);
     }

@@ -79,9 +79,37 @@ __global__ __launch_bounds__(AI_BLOCK) void kp_radius_mean(const double* __restr
   if (t == 0 && count) count[i] = cnt;
 }
 
-// One thread per fine point: exact nearest source point (smallest sq_dist3, ties to the smaller
-// source index; distance = its correctly rounded sqrt) by growing rings of cells; a ring r can
-// only hold points at distance > (r - 1) * cell, so the search stops once best <= r * cell.
+// The distances from x to the two faces, on one axis, of the box of rings 0..r around cell c: the planes min + (c - r) * cell and
+// min + (c + r + 1) * cell.  A side on which the grid has no cell left counts as infinitely far.  Every step is rounded on its own
+// (no contraction), so that the slack of kp_nn1's stop rule can be counted and tests/points_cases.py can restate it.
+__device__ __forceinline__ double face_gap(double x, double mn, double cell, int c, int r, int n) {
+#pragma clang fp contract(off)
+  const double lo = (c - r - 1 >= 0) ? x - (mn + (double)(c - r) * cell) : INFINITY;
+  const double hi = (c + r + 1 <= n - 1) ? (mn + (double)(c + r + 1) * cell) - x : INFINITY;
+  return fmin(lo, hi);
+}
+
+// |min| + (n + 1) * cell + |x|: above every magnitude that enters an index or a face on this axis
+__device__ __forceinline__ double axis_mag(double x, double mn, double cell, int n) {
+#pragma clang fp contract(off)
+  return (fabs(mn) + (double)(n + 1) * cell) + fabs(x);
+}
+
+// One thread per fine point: exact nearest source point (smallest sq_dist3, ties to the smaller source index; distance = its
+// correctly rounded sqrt) by growing rings of cells.
+// Stop rule (kn_nearest's, ai_prep.hip): a source outside rings 0..r has, on some axis, a stored cell index k >= c + r + 1 (or
+// <= c - r - 1), so it lies beyond that face F = min + k * cell of the box of those rings -- up to the rounding of pcell_of.  With
+// u = 2^-53: the index is floor(fl(fl(p - min) * inv_cell)) and inv_cell = fl(1 / cell), three roundings, so fl(..) >= k only
+// gives p - min >= k * cell * (1 - 4u) (and < k * cell * (1 + 4u) on the low side; the clamp to n - 1 only lowers a stored index):
+// the source may lie 4u * k * cell inside the face.  face_gap computes |F - x| with three more roundings, of k * cell, of F and
+// of the difference: at most u * (k * cell + |F| + |F| + |x|) off.  With mag >= |min| + (n + 1) * cell + |x| on every axis, which
+// bounds k * cell, |F| and |x|, all of it stays below 8u * mag; `slack` is 16u * mag = 8 ulps of mag, as in kn_nearest.  So every
+// unvisited source is more than lb = (nearest face gap) - slack away, in exact arithmetic.  sq_dist3 rounds five times, hence
+// returns at least d^2 * (1 - 5u) for a source at distance d > lb; sqrt(best) * (1 + 8u) <= lb gives best <= lb^2 * (1 - 11u)
+// after the rounding of the sqrt and of the product: strictly below the square of every unvisited source, so none is nearer or
+// tied.  The face gap is at least r * cell, the bound the rule had before the rounding was counted (a source that fl(p - min)
+// had rounded up onto a cell border was missed when best == r * cell): an extra ring is searched only when sqrt(best) is within
+// the slack of it.  With no cell left on any side lb is +inf and the loop ends.
 __global__ __launch_bounds__(AI_BLOCK) void kp_nn1(const double* __restrict__ q, int64_t nq, PGrid g, double cell,
                                                    const double* __restrict__ X, const double* __restrict__ Y,
                                                    const double* __restrict__ Z, const int32_t* __restrict__ order,
@@ -90,13 +118,16 @@ __global__ __launch_bounds__(AI_BLOCK) void kp_nn1(const double* __restrict__ q,
   const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
   if (i >= nq) return;
   const double x = q[i * 3], y = q[i * 3 + 1], z = q[i * 3 + 2];
+  if (!(fabs(x) < INFINITY && fabs(y) < INFINITY && fabs(z) < INFINITY)) {
+    // no square of a NaN or infinite query compares below any other: no nearest source, and no walk over the whole grid
+    nn_idx[i] = -1;
+    if (nn_dist) nn_dist[i] = NAN;
+    return;
+  }
   int cx, cy, cz;
   pcell_of(g, x, y, z, cx, cy, cz);
-  // distance from the query to its (clamped) home cell: queries outside the box start further out
-  const double ox = fmax(fmax(g.minx - x, x - (g.minx + g.nx * cell)), 0.0);
-  const double oy = fmax(fmax(g.miny - y, y - (g.miny + g.ny * cell)), 0.0);
-  const double oz = fmax(fmax(g.minz - z, z - (g.minz + g.nz * cell)), 0.0);
-  const double outside = sqrt(ox * ox + oy * oy + oz * oz);
+  const double eps = 2.220446049250313e-16;
+  const double slack = 8.0 * eps * fmax(fmax(axis_mag(x, g.minx, cell, g.nx), axis_mag(y, g.miny, cell, g.ny)), axis_mag(z, g.minz, cell, g.nz));
   double best = 1e300;
   int32_t bi = -1;
   const int rmax = max(g.nx, max(g.ny, g.nz));
@@ -126,8 +157,8 @@ __global__ __launch_bounds__(AI_BLOCK) void kp_nn1(const double* __restrict__ q,
         }
       }
     }
-    // every unvisited point sits in ring >= r + 1, i.e. at least r * cell away from the home cell
-    if (bi >= 0 && sqrt(best) <= (double)r * cell - outside) break;
+    const double lb = fmin(face_gap(x, g.minx, cell, cx, r, g.nx), fmin(face_gap(y, g.miny, cell, cy, r, g.ny), face_gap(z, g.minz, cell, cz, r, g.nz))) - slack;
+    if (bi >= 0 && sqrt(best) * (1.0 + 4.0 * eps) <= lb) break;
   }
   nn_idx[i] = bi;
   if (nn_dist) nn_dist[i] = sqrt(best);

@@ -264,10 +264,15 @@ def tarl_features_per_map(dataset, chunk_downsample_dict, T_pcd, sampled_indices
 
 
 def nn1_index(points_to, points_from, *, ctx: Context | None = None):
-    """(index[Nt] int32, distance[Nt] float64) of the nearest `points_from` row for every `points_to` row."""
+    """(index[Nt] int32, distance[Nt] float64) of the nearest `points_from` row for every `points_to` row.
+
+    A NaN or infinite coordinate in ``points_to`` raises ``ValueError``: ``ai_nn1_project`` answers such a row with index -1,
+    which as a NumPy index would silently mean the last source."""
     ctx = ctx or default_context()
     t = np.ascontiguousarray(points_to, dtype=np.float64)
     f = np.ascontiguousarray(points_from, dtype=np.float64)
+    if not np.isfinite(t).all():
+        raise ValueError("nn1_index: points_to has NaN or infinite coordinates, which have no nearest point")
     idx = np.empty(t.shape[0], dtype=np.int32)
     dist = np.empty(t.shape[0], dtype=np.float64)
     _ffi.check(_ffi.load().ai_nn1_project(ctx._h, t.ctypes.data, t.shape[0], f.ctypes.data, f.shape[0], _ffi.AI_MEM_HOST,
@@ -279,6 +284,8 @@ def nn1_reproject(features_to, points_to, features_from, points_from, max_radius
                   ctx: Context | None = None):
     """Drop-in arithmetic of ``kDTree_1NN_feature_reprojection`` on arrays (no open3d objects)."""
     features_to = np.array(features_to, copy=True)
+    if not np.isfinite(np.asarray(points_to, dtype=np.float64)).all():
+        raise ValueError("nn1_reproject: points_to has NaN or infinite coordinates, no feature can be re-projected onto them")
     idx, dist = nn1_index(points_to, points_from, ctx=ctx)
     features_to[:] = np.asarray(features_from)[idx]
     if max_radius is not None:

@@ -240,7 +240,9 @@ int ai_eigs_smallest(ai_ctx* ctx, const ai_csr* csr, int32_t k, const ai_ncut_op
  *   row when there is none); count_out[i] (may be NULL) = how many.  dim <= 384.
  * ai_nn1_project: pipeline/utils/point_cloud/point_cloud_utils.py:144-174 (kDTree_1NN_feature_reprojection)
  *   -- nn_index[i] = index of the source point nearest to fine point i, nn_dist[i] (may be NULL) its
- *   distance; the caller gathers labels / colours and applies max_radius.
+ *   distance; the caller gathers labels / colours and applies max_radius.  A fine point with a NaN or infinite coordinate
+ *   has no nearest source: nn_index[i] = -1, nn_dist[i] = NaN.
+ * A NaN or infinite source coordinate is AI_ERR_BAD_ARG ("coordinates are not finite") in both.
  * Buffers are host or device according to mem_kind (all of one kind).
  */
 int ai_radius_mean_pool(ai_ctx* ctx, const double* query_xyz, int64_t nq, const double* src_xyz, int64_t ns,
