@@ -15,26 +15,13 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "ai_common.h"
+#include "ai_xform.h"  // ai_xf: the fixed-order transform (step 1)
 
 namespace {
 
 #include "ai_cells.inc"
 
 #define AI_CAM_MAX_VIEWS 64
-
-// open3d PointCloud::transform of one point: row r = ((T[r,0]*x + T[r,1]*y) + T[r,2]*z) + T[r,3], divided by row 3 (w).
-// T: 16 doubles, row-major.  No contraction (camera_api.transform_points is the same order on the host).
-__device__ __forceinline__ void cam_xf(const double* __restrict__ T, double x, double y, double z, double& ox, double& oy,
-                                       double& oz) {
-#pragma clang fp contract(off)
-  const double a = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-  const double b = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-  const double c = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
-  const double w = ((T[12] * x + T[13] * y) + T[14] * z) + T[15];
-  ox = a / w;
-  oy = b / w;
-  oz = c / w;
-}
 
 // one bit per view in every cloud point that a view's visible set names; an index outside [0, nc) raises *bad
 __global__ __launch_bounds__(AI_BLOCK) void kc_view_bits(const int32_t* __restrict__ vis_index, int64_t total,
@@ -118,8 +105,8 @@ __global__ __launch_bounds__(AI_BLOCK) void kc_visible(const double* __restrict_
                 const int v = __ffsll((long long)m) - 1;
                 m &= m - 1;
                 double qx, qy, qz, ux, uy, uz;
-                cam_xf(T + 16 * v, x, y, z, qx, qy, qz);
-                cam_xf(T + 16 * v, px, py, pz, ux, uy, uz);
+                ai_xf(T + 16 * v, x, y, z, qx, qy, qz);
+                ai_xf(T + 16 * v, px, py, pz, ux, uy, uz);
                 if (sqrt(sq_dist3(qx, qy, qz, ux, uy, uz)) < max_dist) found |= 1ull << v;
               }
             }
@@ -159,7 +146,7 @@ __global__ __launch_bounds__(AI_BLOCK) void kc_project(const double* __restrict_
   int32_t pu = -1, pv = -1;
   if (lane < V && ((seen[i] >> lane) & 1ull)) {
     double x, y, z;
-    cam_xf(T + 16 * lane, q[i * 3], q[i * 3 + 1], q[i * 3 + 2], x, y, z);
+    ai_xf(T + 16 * lane, q[i * 3], q[i * 3 + 1], q[i * 3 + 2], x, y, z);
     const double u1 = (P.K[0] * x + P.K[1] * y) + P.K[2] * z;
     const double v1 = (P.K[3] * x + P.K[4] * y) + P.K[5] * z;
     const double w1 = (P.K[6] * x + P.K[7] * y) + P.K[8] * z;

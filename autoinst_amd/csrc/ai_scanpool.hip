@@ -22,6 +22,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "ai_common.h"
+#include "ai_xform.h"  // ai_xf: the fixed-order transform (R1)
 
 namespace {
 
@@ -63,19 +64,6 @@ __device__ __forceinline__ int32_t sp_segment_of(const int64_t* __restrict__ off
   return a;
 }
 
-// R1: open3d PointCloud::transform in the project's fixed order (camera_api.transform_points, cam_xf of ai_camera.hip): row r =
-// ((T[r,0]*x + T[r,1]*y) + T[r,2]*z) + T[r,3], divided by row 3.  No contraction.
-__device__ __forceinline__ void sp_xf(const double* __restrict__ T, double x, double y, double z, double& ox, double& oy, double& oz) {
-#pragma clang fp contract(off)
-  const double a = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-  const double b = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-  const double c = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
-  const double w = ((T[12] * x + T[13] * y) + T[14] * z) + T[15];
-  ox = a / w;
-  oy = b / w;
-  oz = c / w;
-}
-
 __device__ __forceinline__ bool sp_in_box(const SPChunk& c, double x, double y, double z) {
   return x > c.lo[0] && y > c.lo[1] && z > c.lo[2] && x < c.hi[0] && y < c.hi[1] && z < c.hi[2];
 }
@@ -84,7 +72,7 @@ __device__ __forceinline__ bool sp_in_box(const SPChunk& c, double x, double y, 
 __device__ __forceinline__ int32_t sp_source(const double* __restrict__ xyz, const int64_t* __restrict__ scan_off, int32_t n_scans,
                                              const double* __restrict__ T, int64_t i, double& x, double& y, double& z) {
   const int32_t s = sp_segment_of(scan_off, n_scans, i);
-  sp_xf(T + (int64_t)s * 16, xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2], x, y, z);
+  ai_xf(T + (int64_t)s * 16, xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2], x, y, z);
   return s;
 }
 

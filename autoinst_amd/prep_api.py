@@ -22,7 +22,13 @@ called at ``run_pipeline.py:129``) on arrays instead of open3d clouds.
   and every minor point takes the label of its nearest RAW point (the four KD-tree loops of ``:299-370``).  Nearest = smallest
   ``(dx*dx + dy*dy) + dz*dz``, ties to the smaller raw index: the tie rule is ours, open3d's KD-tree defines none.  Not
   reproduced: the order of open3d's hash map (ours is ascending voxel order), open3d's choice among tied points, and the
-  coloured clouds of ``color_pcd_by_labels``, which the reference only uses as KD-tree carriers.
+  coloured clouds of ``color_pcd_by_labels``, which the reference only uses as KD-tree carriers;
+* `aggregate_scans` / `aggregate_pointcloud` -- the head of the chain, ``aggregate_pointcloud``
+  (``pipeline/utils/point_cloud/aggregate_pointcloud.py:12-188``, called at ``run_pipeline.py:102``) with the dataset's filter
+  chain and label decodes: all scans of a map go to the two aggregated raw clouds in one device call (``csrc/ai_aggregate.hip``,
+  rules A1-A6 in ``include/autoinst_hip.h``).  The ground segmentation itself (Patchwork++) stays an input: per-scan masks or
+  index lists.  Not reproduced: ICP registration, open3d's RANSAC plane, and the order of the ground segmentation's index list
+  (each map is in ascending input position).
 
 All kernels are HIP (``csrc/ai_prep.hip``); there is no CPU fallback.  Inputs are NumPy arrays or float64 torch tensors
 on the context's GPU; device inputs give device outputs, so map -> major chunks -> `ncuts_api.build_affinity` /
@@ -297,3 +303,298 @@ def chunk_and_downsample_point_clouds(pcd_nonground_minor, pcd_ground_minor, T_p
         "kitti_labels": {"nonground": k_ng, "ground": k_gr},
         "obbs": obbs,
     }
+
+
+AGGREGATE_LABEL_KINDS = ("seg", "instance", "panoptic")   # aggregate_pointcloud.py:175-182
+
+
+def _scan_offsets(lengths):
+    off = np.zeros(len(lengths) + 1, dtype=np.int64)
+    np.cumsum(np.asarray(lengths, dtype=np.int64), out=off[1:])
+    return off
+
+
+def _scan_points(scan_points, scan_offsets):
+    """(xyz (M, 3) float32 contiguous array or device tensor, offsets (n_scans + 1) int64) of either input form."""
+    if isinstance(scan_points, (list, tuple)):
+        if scan_offsets is not None:
+            raise ValueError("scan_offsets goes with one (M, 3) array, not with a list of scans")
+        if any(_is_device_tensor(p) for p in scan_points):
+            import torch
+            if not all(_is_device_tensor(p) and p.dtype == torch.float32 and p.dim() == 2 and p.shape[1] in (3, 4) for p in scan_points):
+                raise ValueError("scans on the device must all be float32 (n, 3) or (n, 4) tensors")
+            off = _scan_offsets([int(p.shape[0]) for p in scan_points])
+            return torch.cat([p[:, :3] for p in scan_points]).contiguous(), off
+        parts = []
+        for k, p in enumerate(scan_points):
+            a = np.asarray(p)
+            if a.size == 0:
+                a = np.zeros((0, 3), dtype=np.float32)
+            if a.dtype != np.float32 or a.ndim != 2 or a.shape[1] not in (3, 4):
+                raise ValueError(f"scan {k} must be a float32 (n, 3) or (n, 4) array, as dataset.get_point_cloud returns it")
+            parts.append(a[:, :3])
+        xyz = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0, 3), dtype=np.float32)
+        return xyz, _scan_offsets([a.shape[0] for a in parts])
+    if scan_offsets is None:
+        raise ValueError("one array of points needs scan_offsets=")
+    off = np.ascontiguousarray(np.asarray(scan_offsets, dtype=np.int64).reshape(-1))
+    if off.shape[0] < 1:
+        raise ValueError("scan_offsets must hold n_scans + 1 entries")
+    if _is_device_tensor(scan_points):
+        import torch
+        if scan_points.dtype != torch.float32 or scan_points.dim() != 2 or scan_points.shape[1] != 3:
+            raise ValueError("scan_points on the device must be a float32 (M, 3) tensor")
+        xyz = scan_points.contiguous()
+    else:
+        xyz = np.asarray(scan_points)
+        if xyz.size == 0:
+            xyz = np.zeros((0, 3), dtype=np.float32)
+        if xyz.dtype != np.float32 or xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError("scan_points must be a float32 (M, 3) array")
+        xyz = np.ascontiguousarray(xyz)
+    if int(off[-1]) != int(xyz.shape[0]):
+        raise ValueError(f"scan_offsets ends at {int(off[-1])} for {int(xyz.shape[0])} points")
+    return xyz, off
+
+
+def _label_words(labels, off, like):
+    """The raw label words of all scans as one buffer of 32-bit words where `like` lives (device: an int32 tensor with the
+    words' bits).  Any integer dtype whose values fit uint32."""
+    M = int(off[-1])
+    if isinstance(labels, (list, tuple)):
+        if len(labels) != off.shape[0] - 1:
+            raise ValueError(f"{len(labels)} label arrays for {off.shape[0] - 1} scans")
+        if any(_is_device_tensor(a) for a in labels):
+            import torch
+            labels = torch.cat([a.reshape(-1) for a in labels]) if labels else torch.zeros(0, dtype=torch.int64, device=like.device)
+        else:
+            for k, a in enumerate(labels):
+                if np.asarray(a).size != off[k + 1] - off[k]:
+                    raise ValueError(f"labels of scan {k} have {np.asarray(a).size} entries for {off[k + 1] - off[k]} points")
+            labels = np.concatenate([np.asarray(a).reshape(-1) for a in labels]) if labels else np.zeros(0, dtype=np.uint32)
+    if _is_device_tensor(labels):
+        import torch
+        t = labels.reshape(-1)
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+            raise ValueError("labels must be an integer tensor")
+        if t.shape[0] != M:
+            raise ValueError(f"labels have {t.shape[0]} entries for {M} points")
+        if t.dtype == getattr(torch, "uint32", None):
+            words = t.contiguous().view(torch.int32)
+        else:
+            t = t.to(torch.int64)
+            if M and (int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF):
+                raise ValueError("a label word does not fit uint32")
+            words = torch.where(t >= 2 ** 31, t - 2 ** 32, t).to(torch.int32)
+        return words.to(like.device) if _is_device_tensor(like) else words.cpu().numpy().view(np.uint32)
+    a = np.asarray(labels).reshape(-1)
+    if a.dtype.kind not in "iu":
+        raise ValueError("labels must be an integer array")
+    if a.shape[0] != M:
+        raise ValueError(f"labels have {a.shape[0]} entries for {M} points")
+    if a.dtype != np.uint32:
+        if M and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ValueError("a label word does not fit uint32")
+        a = a.astype(np.uint32)
+    a = np.ascontiguousarray(a)
+    if _is_device_tensor(like):
+        import torch
+        return torch.as_tensor(a.view(np.int32), device=like.device)
+    return a
+
+
+def _ground_flags(ground, off, like):
+    """One byte per input point, non-zero = ground, from per-scan boolean masks or per-scan index lists (which index the INPUT
+    scan: a duplicate or out-of-range index is a ValueError), or from one (M,) mask."""
+    M = int(off[-1])
+    if _is_device_tensor(ground):
+        import torch
+        if ground.reshape(-1).shape[0] != M:
+            raise ValueError(f"ground has {ground.reshape(-1).shape[0]} entries for {M} points")
+        flags = (ground.reshape(-1) != 0).to(torch.uint8).contiguous()
+        return flags.to(like.device) if _is_device_tensor(like) else flags.cpu().numpy()
+    if isinstance(ground, np.ndarray) and ground.dtype == np.bool_ and ground.ndim == 1:      # one mask for all scans
+        if ground.shape[0] != M:
+            raise ValueError(f"a ground mask for all scans must have {M} entries")
+        ground = [ground[off[k]:off[k + 1]] for k in range(off.shape[0] - 1)]
+    if len(ground) != off.shape[0] - 1:
+        raise ValueError(f"{len(ground)} ground entries for {off.shape[0] - 1} scans")
+    flags = np.zeros(M, dtype=np.uint8)
+    for k, g in enumerate(ground):
+        n = int(off[k + 1] - off[k])
+        g = np.asarray(g.cpu() if _is_device_tensor(g) else g).reshape(-1)
+        view = flags[off[k]:off[k + 1]]
+        if g.dtype == np.bool_:
+            if g.shape[0] != n:
+                raise ValueError(f"the ground mask of scan {k} has {g.shape[0]} entries for {n} points")
+            view[g] = 1
+        else:
+            if g.size and g.dtype.kind not in "iu":
+                raise ValueError(f"the ground entry of scan {k} must be a boolean mask or an integer index array")
+            g = g.astype(np.int64)
+            if g.size and (int(g.min()) < 0 or int(g.max()) >= n):
+                raise ValueError(f"a ground index of scan {k} is outside [0, {n})")
+            if np.unique(g).shape[0] != g.shape[0]:
+                raise ValueError(f"the ground indices of scan {k} hold a duplicate")
+            view[g] = 1
+    if _is_device_tensor(like):
+        import torch
+        return torch.as_tensor(flags, device=like.device)
+    return flags
+
+
+def _widen_words(a):
+    """uint32 bits held in an int32 device tensor -> int64 values: one cast where torch casts uint32, else a cast and a mask."""
+    import torch
+    if hasattr(torch, "uint32"):
+        try:
+            return a.view(torch.uint32).to(torch.int64)
+        except (RuntimeError, TypeError):   # a build whose uint32 has no cast on this device
+            pass
+    return a.to(torch.int64) & 0xFFFFFFFF
+
+
+def aggregate_scans(scan_points, poses, *, labels=None, ground=None, moving_index=None, range_min=None, range_max=None,
+                    return_source=False, scan_offsets=None, ctx: Context | None = None):
+    """All scans of a map to the two aggregated raw clouds in one device call (``ai_aggregate_scans``): the loop of
+    ``aggregate_pointcloud`` (``aggregate_pointcloud.py:99-186``) with the dataset's filters (``kitti_gt_mo_filter.py:40-51``,
+    ``range_filter.py:23-36``) and label decodes (``kitti_odometry_dataset.py:73-104``).
+
+    ``scan_points``: a list of float32 ``(n_s, 3)`` or ``(n_s, 4)`` arrays in their sensor frames, as
+    ``dataset.get_point_cloud`` returns them (column 3, the intensity, is ignored), or one float32 ``(M, 3)`` array / device
+    tensor with ``scan_offsets=`` (``n_scans + 1`` entries).  ``poses``: ``(n_scans, 4, 4)``, last rows exactly ``0 0 0 1``.
+    ``labels``: the raw ``.label`` words, in the same forms, uint32 or any integer dtype whose values fit.  ``ground``: per-scan
+    boolean masks or per-scan index arrays into the INPUT scan (what Patchwork++'s ``getGroundIndices`` returns), or ``None``
+    (every kept point is non-ground).  ``moving_index`` (the reference's 251) keeps a point iff ``(word & 0xFFFF) <
+    moving_index``; ``range_min`` / ``range_max`` keep it iff its float32 norm lies in ``[range_min, range_max]``, both ends
+    inclusive; ``None`` switches a filter off (``range_min`` alone defaults the other end to 0 / infinity).
+
+    Returns ``(pcd_ground, pcd_nonground, labels_dict)``: float64 ``(n, 3)`` clouds in the map frame, each in ascending input
+    position, and (when ``labels`` is given) ``seg_*``, ``instance_*``, ``panoptic_*`` for ``ground`` and ``nonground`` as
+    ``(n,)`` arrays -- ``np.uint32`` on the host; int64 tensors holding the same values on the device (torch's uint32 cannot
+    index).  ``instance`` is the reference's ``(word & 0xFFFF0000) * (word & 0xFFFF + 10)``, i.e. the mask 0x10009 and a product
+    modulo 2^32.  With ``return_source`` also ``source_ground`` / ``source_nonground`` (int64: the input position of every output
+    point) and ``offsets_ground`` / ``offsets_nonground`` (host int64, ``n_scans + 1``: where each scan's run starts).  Device
+    points give device outputs; the result goes unchanged into ``downsample_map(pcd_nonground, pcd_ground, labels_dict)``.
+
+    `scan_calibration_stays_on_host`: the vertical-angle correction of ``_correct_scan_calibration``
+    (``kitti_odometry_dataset.py:306-335``) is NOT part of this call.  Its float32 result depends on NumPy's scalar promotion
+    rules (which differ between NumPy 1.24 and 2.x) and on ``einsum``'s summation order, and ``get_point_cloud`` caches it
+    anyway: pass the scans as the dataset returns them."""
+    ctx = ctx or default_context()
+    xyz, off = _scan_points(scan_points, scan_offsets)
+    n_scans, M = off.shape[0] - 1, int(xyz.shape[0])
+    T = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 16))
+    if T.shape[0] != n_scans:
+        raise ValueError(f"{T.shape[0]} poses for {n_scans} scans")
+    words = _label_words(labels, off, xyz) if labels is not None else None
+    flags = _ground_flags(ground, off, xyz) if ground is not None else None
+    if range_min is None and range_max is None:
+        rmin, rmax = 0.0, -1.0
+    else:
+        rmin = 0.0 if range_min is None else float(range_min)
+        rmax = float("inf") if range_max is None else float(range_max)
+        if rmax < 0.0:
+            raise ValueError("range_max must not be negative")
+    ptr, mem, torch = _call_args(xyz)
+    cap = max(M, 1)
+    if torch:
+        def new(shape, dtype):
+            return torch.empty(shape, dtype=dtype, device=xyz.device)
+
+        def addr(a):
+            return C.c_void_p(a.data_ptr()) if a is not None else None
+        f64, i32, u32 = torch.float64, torch.int32, torch.int32
+    else:
+        def new(shape, dtype):
+            return np.empty(shape, dtype=dtype)
+
+        def addr(a):
+            return a.ctypes.data if a is not None else None
+        f64, i32, u32 = np.float64, np.int32, np.uint32
+    out = {c: new((cap, 3), f64) for c in ("ground", "nonground")}
+    lab = {f"{k}_{c}": (new(cap, u32) if words is not None else None) for k in AGGREGATE_LABEL_KINDS for c in ("ground", "nonground")}
+    src = {c: (new(cap, i32) if return_source else None) for c in ("ground", "nonground")}
+    class_off = np.zeros(2 * (n_scans + 1), dtype=np.int64)
+    ng, nn = C.c_int64(0), C.c_int64(0)
+    _ffi.check(_ffi.load().ai_aggregate_scans(
+        ctx._h, ptr, off.ctypes.data, n_scans, T.ctypes.data, addr(words), addr(flags), -1 if moving_index is None else int(moving_index),
+        rmin, rmax, mem, addr(out["ground"]), addr(out["nonground"]), addr(lab["seg_ground"]), addr(lab["seg_nonground"]),
+        addr(lab["instance_ground"]), addr(lab["instance_nonground"]), addr(lab["panoptic_ground"]), addr(lab["panoptic_nonground"]),
+        addr(src["ground"]), addr(src["nonground"]), class_off.ctypes.data, C.byref(ng), C.byref(nn)), "ai_aggregate_scans")
+    count = {"ground": ng.value, "nonground": nn.value}
+    labels_dict = {}
+    for key, a in lab.items():
+        if a is not None:
+            a = a[:count[key.split("_")[1]]]
+            labels_dict[key] = _widen_words(a) if torch else a
+    if return_source:
+        for i, c in enumerate(("ground", "nonground")):
+            s = src[c][:count[c]]
+            labels_dict[f"source_{c}"] = s.long() if torch else s.astype(np.int64)
+            labels_dict[f"offsets_{c}"] = class_off[i * (n_scans + 1):(i + 1) * (n_scans + 1)].copy()
+    return out["ground"][:ng.value], out["nonground"][:nn.value], labels_dict
+
+
+def _patchwork_segmenter():
+    try:
+        import pypatchworkpp
+    except ImportError as e:
+        raise ImportError('ground_segmentation="patchwork" needs the pypatchworkpp module (Patchwork++ is an external C++ library that '
+                          "is not part of this package): install it, or pass a callable (points, intensity) -> ground indices") from e
+    params = pypatchworkpp.Parameters()
+    params.verbose = False
+    model = pypatchworkpp.patchworkpp(params)
+
+    def segment(points, intensity):
+        model.estimateGround(np.hstack((points, np.asarray(intensity).reshape(-1, 1))))
+        return model.getGroundIndices()
+    return segment
+
+
+def aggregate_pointcloud(dataset, ind_start, ind_end, ground_segmentation=None, icp=False, *, ctx: Context | None = None):
+    """Drop-in for ``aggregate_pointcloud`` (``aggregate_pointcloud.py:12``): reads ``dataset[i]`` (already filtered by the
+    dataset's own chain) and ``dataset.get_pose(i)`` for ``ind_start <= i < ind_end`` and makes ONE `aggregate_scans` call with
+    the filters off.  ``ground_segmentation``: ``None``; a callable ``(points (n, 3), intensity (n,)) -> ground indices``; or
+    ``"patchwork"``, which imports ``pypatchworkpp`` (``ImportError`` when it is missing).  Returns the reference's
+    ``(map_pcd_ground, map_pcd_nonground, poses, world_pose, labels)`` with ``(n, 3)`` float64 arrays for the clouds and, per
+    key of ``labels``, the ``(n, 1)`` column that ``np.vstack`` makes of the reference's per-scan lists
+    (``dataset_utils.py:193-196``); with ``ground_segmentation=None`` the 2-tuple ``(map_pcd, poses)``.
+
+    ``"open3d"`` raises ``NotImplementedError``: its plane comes from open3d's RANSAC with an unseeded random generator, so there
+    is nothing to reproduce.  ``icp=True`` raises too: ICP registration is not ported.  The scan calibration correction stays
+    on the host, inside the dataset (see `aggregate_scans`)."""
+    if icp:
+        raise NotImplementedError("icp=True: ICP registration (open3d registration_icp against the growing map) is not ported")
+    if isinstance(ground_segmentation, str):
+        if ground_segmentation == "open3d":
+            raise NotImplementedError('ground_segmentation="open3d" is a RANSAC plane from an unseeded random generator: '
+                                      "it has no reproducible result to port")
+        if ground_segmentation != "patchwork":
+            raise ValueError('ground_segmentation must be None, "patchwork", "open3d" or a callable')
+        ground_segmentation = _patchwork_segmenter()
+    scans, poses, ground = [], [], []
+    cols = {k: [] for k in AGGREGATE_LABEL_KINDS}
+    for i in range(ind_start, ind_end):
+        entry = dataset[i]
+        p = np.asarray(entry.point_cloud)[:, :3]
+        p32 = np.ascontiguousarray(p, dtype=np.float32)
+        if p.dtype != np.float32 and not np.array_equal(p32, p):
+            raise ValueError(f"the point cloud of entry {i} is not float32 (dataset.get_point_cloud returns float32)")
+        scans.append(p32)
+        poses.append(np.asarray(dataset.get_pose(i), dtype=np.float64))
+        if ground_segmentation is not None:
+            ground.append(np.asarray(ground_segmentation(p32, np.asarray(entry.intensity).reshape(-1))).reshape(-1))
+            for kind, attr in (("seg", "semantic_labels"), ("instance", "instance_labels"), ("panoptic", "panoptic_labels")):
+                cols[kind].append(np.asarray(getattr(entry, attr)).reshape(-1, 1))
+    stacked = np.stack(poses) if poses else np.zeros((0, 4, 4))
+    if ground_segmentation is None:
+        _, map_pcd, _ = aggregate_scans(scans, stacked, ctx=ctx)
+        return map_pcd, poses
+    g, ng, info = aggregate_scans(scans, stacked, ground=ground, return_source=True, ctx=ctx)
+    labels = {}
+    for kind in AGGREGATE_LABEL_KINDS:
+        col = np.vstack(cols[kind]) if cols[kind] else np.zeros((0, 1), dtype=np.uint32)
+        for cloud in ("ground", "nonground"):
+            labels[f"{kind}_{cloud}"] = col[info[f"source_{cloud}"]]
+    return g, ng, poses, np.eye(4), labels

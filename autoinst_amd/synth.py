@@ -330,3 +330,55 @@ def rig_sam_masks(rig, view: int):
         seg[r0:r1, c0:c1] = True
         out.append({"segmentation": seg})
     return out
+
+
+def labelled_scans(n_scans: int = 20, points_per_scan: int = 10_000, seed: int = 0, *, spacing: float = 1.5, width: float = 16.0,
+                   reach: float = 40.0, facade_height: float = 8.0, moving_frac: float = 0.03):
+    """A deterministic street as the scans ``aggregate_pointcloud`` reads (``aggregate_pointcloud.py:99-107``): per scan float32
+    points in the sensor frame, raw ``.label`` words, a ground mask (what a ground segmentation would return) and the pose.
+
+    The sensor drives along x, ``spacing`` metres per scan, 1.7 m above the road, with a slow yaw and a little roll; scan lengths
+    vary by a few per cent around ``points_per_scan``.  In the sensor frame a scan sees the road (|x| <= ``reach``, |y| <=
+    ``width`` / 2; semantic 40, flagged ground), the two facades (semantic 50) and box-shaped objects (semantic 10 with an
+    instance number in the upper half of the word; ``moving_frac`` of the points carry a moving class, 252 upwards).  The map
+    frame is the world frame: ``T_pcd`` is the identity and ``first_position`` the origin.
+
+    Returns a dict: ``scans``, ``labels`` (uint32), ``ground`` (bool) -- lists per scan; ``poses`` (n_scans, 4, 4);
+    ``T_pcd``, ``positions``, ``first_position``, ``indices`` for `prep_api.chunk_and_downsample_point_clouds`.
+    """
+    rng = np.random.default_rng(seed)
+    half = np.float32(width / 2.0)
+    scans, labels, ground = [], [], []
+    poses = np.zeros((n_scans, 4, 4))
+    for s in range(n_scans):
+        n = int(points_per_scan * (0.97 + 0.06 * rng.random()))
+        u = rng.random((n, 3), dtype=np.float32)
+        kind = rng.random(n, dtype=np.float32)
+        p = np.empty((n, 3), dtype=np.float32)
+        p[:, 0] = (u[:, 0] * 2 - 1) * np.float32(reach)
+        road, left = kind < 0.45, (kind >= 0.45) & (kind < 0.68)
+        right = (kind >= 0.68) & (kind < 0.91)
+        p[:, 1] = (u[:, 1] * 2 - 1) * half
+        p[:, 2] = np.float32(-1.7) + np.float32(0.02) * (u[:, 2] - np.float32(0.5))
+        for side, m in ((-1.0, left), (1.0, right)):
+            p[m, 1] = np.float32(side) * half + np.float32(0.02) * (u[m, 1] - np.float32(0.5))
+            p[m, 2] = np.float32(-1.7) + u[m, 2] * np.float32(facade_height)
+        obj = ~(road | left | right)
+        number = (np.floor((p[:, 0] + np.float32(reach)) / np.float32(6.0)).astype(np.uint32) + np.uint32(s // 4 + 1)) & np.uint32(0xFFFF)
+        p[obj, 1] *= np.float32(0.6)
+        p[obj, 2] = np.float32(-1.7) + u[obj, 2] * np.float32(1.8)
+        sem = np.where(road, 40, np.where(obj, 10, 50)).astype(np.uint32)
+        moving = obj & (rng.random(n, dtype=np.float32) < moving_frac / 0.09)
+        sem[moving] = np.uint32(252) + (number[moving] % np.uint32(8))
+        words = sem | np.where(obj, number << np.uint32(16), np.uint32(0))
+        yaw, roll = 0.002 * s, 0.01 * np.sin(0.3 * s)
+        T = np.eye(4)
+        T[:3, :3] = _rotation((0.0, 0.0, 1.0), yaw) @ _rotation((1.0, 0.0, 0.0), roll)
+        T[:3, 3] = [spacing * s, 0.05 * np.sin(0.7 * s), 1.7]
+        poses[s] = T
+        scans.append(p)
+        labels.append(words.astype(np.uint32))
+        ground.append(road)
+    positions = poses[:, :3, 3].copy()
+    return {"scans": scans, "labels": labels, "ground": ground, "poses": poses, "T_pcd": np.eye(4), "positions": positions,
+            "first_position": np.zeros(3), "indices": np.arange(n_scans, dtype=np.int64)}

@@ -383,6 +383,49 @@ int ai_scan_pool(ai_ctx* ctx, const double* scan_xyz, const int64_t* scan_off, i
                  const double* boxes, const int32_t* scan_win, double radius, int mem_kind, double* out, int32_t* count_out);
 
 /*
+ * The aggregated raw clouds of a map from its scans in one call: the loop of aggregate_pointcloud (pipeline/utils/point_cloud/
+ * aggregate_pointcloud.py:99-186) with the dataset's filter chain (pipeline/dataset/filters/kitti_gt_mo_filter.py:40-51,
+ * range_filter.py:23-36) and the three label decodes (pipeline/dataset/kitti_odometry_dataset.py:73-104).
+ * scan_xyz holds all scans one after the other, each in its own sensor frame, float32 as the dataset returns them (scan s: rows
+ * scan_off[s] .. scan_off[s+1]); pose[s] takes scan s to the map frame; label_word (may be NULL) the raw .label words;
+ * ground_flag (may be NULL) one byte per INPUT point, non-zero = ground (the ground segmentation itself stays the caller's).
+ *   A1 Moving-object filter.  With moving_index >= 0 a point is kept iff (label_word & 0xFFFF) < moving_index (the reference's
+ *      value is 251); moving_index < 0 switches the filter off.  The filter without label_word is AI_ERR_BAD_ARG.
+ *   A2 Range filter (is_centered = True).  s = (x*x + y*y) + z*z in float32, every step rounded, no contraction; r = the correctly
+ *      rounded float32 square root of s; kept iff r >= (float)range_min && r <= (float)range_max, both ends inclusive.  A NaN
+ *      coordinate fails both comparisons and is dropped, as in NumPy.  range_max < 0 switches the filter off.
+ *   A3 Class.  A kept point is ground iff ground_flag is given and non-zero there, else non-ground; with ground_flag == NULL every
+ *      kept point is non-ground (the reference's ground_segmentation=None branch, :46-87).
+ *   A4 Transform.  The float32 coordinates are widened to float64 (exact), then rule R1 of ai_scan_pool: row r = ((T[r,0]*x +
+ *      T[r,1]*y) + T[r,2]*z) + T[r,3], divided by row 3, every step rounded on its own.  A last row of a pose other than exactly
+ *      (0, 0, 0, 1) is AI_ERR_BAD_ARG.
+ *   A5 Order.  Each output map holds its points in ascending input position: scan after scan (the reference's map += pcd),
+ *      ascending index within a scan -- a stable partition.  The order within a scan is ours: the reference's is that of the
+ *      index list its ground segmentation returns.
+ *   A6 Labels, per kept point from its word w, all in uint32 arithmetic: seg = w & 0xFFFF; panoptic = (w & 0xFFFF0000) if that
+ *      is not 0, else w & 0xFFFF; instance = (w & 0xFFFF0000) * (w & 0x10009) modulo 2^32.  The reference writes
+ *      `labels_orig & 0xFFFF + 10` (:102), and + binds before &: the mask really is 0x10009, and the uint32 product wraps.  That
+ *      is reproduced, not mended.
+ *   Limits and errors.  M = scan_off[n_scans] < 2^31 - 256, as for ai_box_select.  AI_ERR_BAD_ARG: an offset array that does not
+ *      start at 0 or decreases; a non-finite pose entry; range_min > range_max (or a NaN bound) while the range filter is on; a
+ *      label output without label_word.  Not errors: n_scans == 0, a scan with no points, a call in which nothing survives or in
+ *      which everything is ground.  The arguments are checked in full before any output is written.
+ * Outputs, per class: out_xyz_* (float64, capacity M x 3), out_seg_*, out_instance_*, out_panoptic_* (uint32, capacity M) and
+ * out_src_* (int32, capacity M: the input position of every output point).  The label outputs and out_src_* may be NULL each.
+ * class_off (HOST, 2 x (n_scans + 1) int64, may be NULL): row 0 where each scan's run starts in the ground map, row 1 in the
+ * non-ground map; entry n_scans of a row is the map's size, also returned in *n_ground / *n_nonground (HOST).  scan_xyz,
+ * label_word, ground_flag and the out_* arrays are host or device per mem_kind; scan_off (n_scans + 1) and pose (n_scans x 16
+ * doubles, row-major 4 x 4) are HOST arrays.  Two calls are bit-identical, and a scan's run is the same whether it is aggregated
+ * alone or among others.
+ */
+int ai_aggregate_scans(ai_ctx* ctx, const float* scan_xyz, const int64_t* scan_off, int32_t n_scans, const double* pose,
+                       const uint32_t* label_word, const uint8_t* ground_flag, int32_t moving_index, double range_min,
+                       double range_max, int mem_kind, double* out_xyz_ground, double* out_xyz_nonground, uint32_t* out_seg_ground,
+                       uint32_t* out_seg_nonground, uint32_t* out_instance_ground, uint32_t* out_instance_nonground,
+                       uint32_t* out_panoptic_ground, uint32_t* out_panoptic_nonground, int32_t* out_src_ground,
+                       int32_t* out_src_nonground, int64_t* class_off, int64_t* n_ground, int64_t* n_nonground);
+
+/*
  * Timing hook for bench.py: runs `reps` fused Lanczos SpMV steps on the whole graph as
  * one segment and returns the average kernel time (HIP events on the context's stream)
  * plus the algorithmic byte count of one launch.
