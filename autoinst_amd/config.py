@@ -18,6 +18,7 @@ NUM_TARL_FEATURES = 96      # tarl_extractor.py:84-89 (96-d MinkUNet features)
 NUM_CUTS = 10               # normalized_cut.py:54  get_min_ncut(ev, D, w, 10)
 EIGSH_SIGMA = 1e-10         # normalized_cut.py:49
 MIN_POINTS_METRIC = 200     # metrics_class.py:17
+MEAN_HEIGHT = 0.6           # config.py:68  ground inliers at or above mean z + MEAN_HEIGHT are cut (ncuts_utils.py:193-197)
 
 # config.py:6-37 -- the three shipped NCuts configurations
 CONFIG_SPATIAL = dict(name="spatial_1.0_t_0.075", alpha=1.0, theta=0.0, gamma=0.0, beta=0.0, T=0.075)

@@ -7,6 +7,10 @@
 * `tarl_pool_map` / `tarl_features_per_map` -- the same pooling for every chunk of a map in one device call
   (``ai_scan_pool``, ``csrc/ai_scanpool.hip``): the pose transform, the crop to each chunk's box, the choice of each
   chunk's scans and the radius mean (``chunk_generation.py:221-256``), with every scan read and uploaded once.
+* `finish_chunks` / `finish_map` / `get_corrected_ground` -- the tail of ``ncuts_chunk`` (``pipeline/ncuts/ncuts_utils.py:
+  177-204``) and ``get_corrected_ground`` (``point_cloud_utils.py:331-342``) for every chunk of a map in one device call
+  (``ai_chunk_finish``, ``csrc/ai_finish.hip``): the group of every fine point, the corrected ground and the merged chunk
+  that `labels_api.merge_chunks_unite_instances2` takes.
 All run as HIP kernels over cell lists; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -16,7 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from .config import ADJACENT_FRAMES_TARL, CHUNK_SIZE, MAJOR_VOXEL_SIZE, NUM_TARL_FEATURES, TARL_NORM
+from .config import ADJACENT_FRAMES_TARL, CHUNK_SIZE, MAJOR_VOXEL_SIZE, MEAN_HEIGHT, NUM_TARL_FEATURES, TARL_NORM
 from .ncuts_api import Context, _is_device_tensor, default_context
 
 
@@ -291,3 +295,178 @@ def nn1_reproject(features_to, points_to, features_from, points_from, max_radius
     if max_radius is not None:
         features_to[dist > max_radius] = np.asarray(no_feature_label, dtype=features_to.dtype)
     return features_to
+
+
+FINISH_STATS = ("mean", "std", "threshold", "n_inliers", "mean_z", "z_limit")   # ai_chunk_finish's ground_stats, per chunk
+
+
+def _chunk_labels(major_labels, moff, dev, device):
+    """The group ids of all chunks' major points as one int32 buffer where the points live."""
+    parts = []
+    for c, a in enumerate(major_labels):
+        a = a.reshape(-1) if _is_device_tensor(a) else np.asarray(a).reshape(-1)
+        if int(a.shape[0]) != int(moff[c + 1] - moff[c]):
+            raise ValueError(f"major_labels[{c}] has {int(a.shape[0])} entries for {int(moff[c + 1] - moff[c])} major points")
+        parts.append(a)
+    if dev:
+        import torch
+        parts = [a.to(device=device, dtype=torch.int32) if _is_device_tensor(a) else
+                 torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=device) for a in parts]
+        return torch.cat(parts).contiguous() if parts else torch.zeros(0, dtype=torch.int32, device=device)
+    return np.ascontiguousarray(np.concatenate(parts), dtype=np.int32) if parts else np.zeros(0, dtype=np.int32)
+
+
+def finish_chunks(fine, major, major_labels, ground, *, nb_neighbors=20, std_ratio=2.0, mean_height=MEAN_HEIGHT,
+                  return_stats=False, ctx: Context | None = None):
+    """The tail of ``ncuts_chunk`` (``ncuts_utils.py:185-199``) for all chunks of a map in one device call
+    (``ai_chunk_finish``, rules F1-F7 in ``include/autoinst_hip.h``).
+
+    ``fine``, ``major``, ``ground``: one (n, 3) float64 array or device tensor per chunk -- the minor non-ground chunk points
+    (``pcd_nonground_chunks``), the major-voxel points the cut labelled and the ground chunk points (``pcd_ground_chunks``).
+    ``major_labels``: one integer group id per major point and chunk (what `sharding.run_chunks` returns), or ``None``.
+
+    Per chunk: every fine point takes the group of its nearest major point of the SAME chunk (smallest ``(dx*dx + dy*dy) +
+    dz*dz``, ties to the smaller index); the ground loses open3d's statistical outliers (`prep_api.statistical_inlier_indices`'
+    rules, bit for bit) and then every inlier with ``z >= mean z of the inliers + mean_height``.  Returns one dict per chunk:
+    ``merged_points`` (the fine points, then the kept ground points in ascending order), ``merged_instance`` (int32: group + 1
+    for a fine point, 0 for ground -- the merge's "no instance"), ``fine_instance`` (int32, the group of every fine point) and
+    ``ground_keep`` (int64: the chunk-local indices the reference writes ``[inliers][in_idcs]``).  Without ``major_labels`` the
+    first three are ``None``.  With ``return_stats`` also ``fine_nn`` (int32, chunk-local), ``fine_dist``, ``ground_avg`` and
+    ``stats`` (`FINISH_STATS`).  Device tensors in give device tensors out; only offsets, counts and the statistics cross to the
+    host.  Errors of the list in the header raise ``ValueError``."""
+    ctx = ctx or default_context()
+    n = len(ground)
+    if len(fine) != n or len(major) != n or (major_labels is not None and len(major_labels) != n):
+        raise ValueError("fine, major, major_labels and ground must hold one entry per chunk")
+    every = list(fine) + list(major) + list(ground)
+    dev = any(_is_device_tensor(a) for a in every)
+    device = next(a.device for a in every if _is_device_tensor(a)) if dev else None
+    f, foff = _concat(list(fine), 3, np.float64, "fine", dev, device)
+    m, moff = _concat(list(major), 3, np.float64, "major", dev, device)
+    g, goff = _concat(list(ground), 3, np.float64, "ground", dev, device)
+    lab = _chunk_labels(major_labels, moff, dev, device) if major_labels is not None else None
+    nf, ng = int(foff[-1]), int(goff[-1])
+    if dev:
+        import torch
+
+        def new(shape, dtype):
+            return torch.empty(shape, dtype={np.float64: torch.float64, np.int32: torch.int32}[dtype], device=device)
+
+        def ptr(a):
+            return C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None
+        torch.cuda.current_stream(device).synchronize()   # the concatenations ran on torch's stream, the library reads on its own
+        mem = _ffi.AI_MEM_DEVICE
+    else:
+        def new(shape, dtype):
+            return np.empty(shape, dtype=dtype)
+
+        def ptr(a):
+            return a.ctypes.data if a is not None and a.size else None
+        mem = _ffi.AI_MEM_HOST
+
+    def out_ptr(a):   # an output is never NULL because it is empty: NULL means "not wanted"
+        if a is None:
+            return None
+        return C.c_void_p(a.data_ptr()) if dev else a.ctypes.data
+    nn = new(max(nf, 1), np.int32) if return_stats else None
+    dist = new(max(nf, 1), np.float64) if return_stats else None
+    avg = new(max(ng, 1), np.float64) if return_stats else None
+    keep = new(max(ng, 1), np.int32)
+    flab = new(max(nf, 1), np.int32) if lab is not None else None
+    mxyz = new((max(nf + ng, 1), 3), np.float64) if lab is not None else None
+    mlab = new(max(nf + ng, 1), np.int32) if lab is not None else None
+    koff = np.zeros(n + 1, dtype=np.int64)
+    merged_off = np.zeros(n + 1, dtype=np.int64) if lab is not None else None
+    stats = np.full((n, len(FINISH_STATS)), np.nan)
+    dummy = new(1, np.int32)   # major_label of a call without major points: not NULL (NULL means "no labels"), never read
+    lab_ptr = None if lab is None else out_ptr(lab if (lab.numel() if dev else lab.size) else dummy)
+    _ffi.check(_ffi.load().ai_chunk_finish(
+        ctx._h, ptr(f), foff.ctypes.data, ptr(m), moff.ctypes.data, lab_ptr, ptr(g), goff.ctypes.data, n, int(nb_neighbors),
+        float(std_ratio), float(mean_height), mem, out_ptr(nn), out_ptr(dist), out_ptr(flab), out_ptr(avg), out_ptr(keep),
+        koff.ctypes.data, stats.ctypes.data, out_ptr(mxyz), out_ptr(mlab), merged_off.ctypes.data if merged_off is not None else None),
+        "ai_chunk_finish")
+    res = []
+    for c in range(n):
+        k = keep[koff[c]:koff[c + 1]]
+        d = {"merged_points": None, "merged_instance": None, "fine_instance": None,
+             "ground_keep": k.long() if dev else k.astype(np.int64)}
+        if lab is not None:
+            d["merged_points"] = mxyz[merged_off[c]:merged_off[c + 1]]
+            d["merged_instance"] = mlab[merged_off[c]:merged_off[c + 1]]
+            d["fine_instance"] = flab[foff[c]:foff[c + 1]]
+        if return_stats:
+            d["fine_nn"], d["fine_dist"] = nn[foff[c]:foff[c + 1]], dist[foff[c]:foff[c + 1]]
+            d["ground_avg"] = avg[goff[c]:goff[c + 1]]
+            d["stats"] = {k_: float(v) for k_, v in zip(FINISH_STATS, stats[c])}
+        res.append(d)
+    return res
+
+
+def _chunk_points(a):
+    """(n, 3) points of a dict entry: an array, a device tensor, or an object with ``.points`` (an open3d cloud)."""
+    if not _is_device_tensor(a) and hasattr(a, "points") and not isinstance(a, np.ndarray):
+        a = np.asarray(a.points)
+    return a if _is_device_tensor(a) else np.asarray(a, dtype=np.float64).reshape(-1, 3)
+
+
+def _index(a, idx):
+    """a[idx] where `a` lives (`idx`: int64 array or tensor)."""
+    if _is_device_tensor(a):
+        import torch
+        return a.reshape(-1).index_select(0, idx.to(a.device) if _is_device_tensor(idx) else torch.as_tensor(np.asarray(idx), device=a.device))
+    return np.asarray(a).reshape(-1)[idx.cpu().numpy() if _is_device_tensor(idx) else idx]
+
+
+def _host(a):
+    return a.cpu().numpy() if _is_device_tensor(a) else np.asarray(a)
+
+
+def finish_map(chunk_downsample_dict, labels, *, nb_neighbors=20, std_ratio=2.0, mean_height=MEAN_HEIGHT, color_seed=0,
+               ctx: Context | None = None):
+    """From the cut's labels to the merge's input for a whole map, without open3d: ``chunk_downsample_dict`` is the dict of
+    `prep_api.chunk_and_downsample_point_clouds`, ``labels`` the list `sharding.run_chunks` returns for its
+    ``pcd_nonground_chunks_major_downsampling``.  One `finish_chunks` call.
+
+    Returns ``(chunks, pairs)``.  ``chunks[c]`` holds the five values ``ncuts_chunk`` returns (``ncuts_utils.py:204``) as arrays
+    -- ``merged_chunk`` (points), ``pcd_chunk`` (the fine points), ``cut_hight`` (the kept ground points), ``inst_ground``,
+    ``seg_ground`` (``kitti_labels["ground"][...][c][ground_keep]``; ``None`` without labels in the dict) -- plus
+    ``merged_instance``, ``fine_instance`` and ``ground_keep``; device inputs give device tensors.  ``pairs[c]`` is the host
+    ``(points, colours)`` pair `labels_api.merge_chunks_unite_instances2` takes: the instance as the colour
+    (`formats.labels_to_colors`, seeded per chunk as the reference draws fresh colours per chunk; ground is black)."""
+    from .formats import labels_to_colors
+    fine = [_chunk_points(a) for a in chunk_downsample_dict["pcd_nonground_chunks"]]
+    major = [_chunk_points(a) for a in chunk_downsample_dict["pcd_nonground_chunks_major_downsampling"]]
+    ground = [_chunk_points(a) for a in chunk_downsample_dict["pcd_ground_chunks"]]
+    done = finish_chunks(fine, major, labels, ground, nb_neighbors=nb_neighbors, std_ratio=std_ratio, mean_height=mean_height, ctx=ctx)
+    kitti = (chunk_downsample_dict.get("kitti_labels") or {}).get("ground")
+    chunks, pairs = [], []
+    for c, d in enumerate(done):
+        nf = int(fine[c].shape[0])
+        out = {"merged_chunk": d["merged_points"], "pcd_chunk": d["merged_points"][:nf], "cut_hight": d["merged_points"][nf:],
+               "inst_ground": None, "seg_ground": None, "merged_instance": d["merged_instance"],
+               "fine_instance": d["fine_instance"], "ground_keep": d["ground_keep"]}
+        if kitti is not None:
+            out["inst_ground"] = _index(kitti["instance"][c], d["ground_keep"])                   # ncuts_utils.py:201-202
+            out["seg_ground"] = _index(kitti["semantic"][c], d["ground_keep"])
+        chunks.append(out)
+        pairs.append((_host(d["merged_points"]), labels_to_colors(_host(d["merged_instance"]), seed=color_seed + c)))
+    return chunks, pairs
+
+
+def get_corrected_ground(chunk_downsample_dict, sequence, mean_height=MEAN_HEIGHT, *, ctx: Context | None = None):
+    """Drop-in for ``get_corrected_ground`` (``point_cloud_utils.py:331-342``) on arrays: ``(input_pcd, inst_ground)``, the
+    points of ``pcd_nonground_chunks[sequence]`` followed by the corrected ground of that chunk, and
+    ``kitti_labels["ground"]["instance"][sequence]`` of the kept ground points.  A one-chunk `finish_chunks` call with no fine
+    points."""
+    ground = _chunk_points(chunk_downsample_dict["pcd_ground_chunks"][sequence])
+    nonground = _chunk_points(chunk_downsample_dict["pcd_nonground_chunks"][sequence])
+    if _is_device_tensor(ground):
+        import torch
+        empty = torch.zeros((0, 3), dtype=torch.float64, device=ground.device)
+        cat = torch.cat
+    else:
+        empty = np.zeros((0, 3))
+        cat = np.concatenate
+    d = finish_chunks([empty], [empty], [np.zeros(0, dtype=np.int32)], [ground], mean_height=mean_height, ctx=ctx)[0]
+    inst = chunk_downsample_dict["kitti_labels"]["ground"]["instance"][sequence]
+    return cat([nonground, d["merged_points"]]), _index(inst, d["ground_keep"])

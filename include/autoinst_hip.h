@@ -426,6 +426,50 @@ int ai_aggregate_scans(ai_ctx* ctx, const float* scan_xyz, const int64_t* scan_o
                        int32_t* out_src_nonground, int64_t* class_off, int64_t* n_ground, int64_t* n_nonground);
 
 /*
+ * The tail of ncuts_chunk (pipeline/ncuts/ncuts_utils.py:177-204) and get_corrected_ground (pipeline/utils/point_cloud/
+ * point_cloud_utils.py:331-342) for every chunk of a map in one call: from the group of every major-voxel
+ * point to the merged chunk that merge_chunks_unite_instances2 takes.  All chunks lie one after the other: fine_xyz the minor
+ * non-ground chunk points (chunk c: rows fine_off[c] .. fine_off[c+1]), major_xyz the major-voxel points the cut labelled, with
+ * one group id each in major_label (may be NULL), ground_xyz the ground chunk points.
+ *   F1 Segmentation.  A fine point of chunk c sees only the major rows major_off[c] .. major_off[c+1], a ground point only its
+ *      own chunk's ground rows (chunks overlap in space).
+ *   F2 Nearest major point: the rule of ai_nn1_project.  Smallest (dx*dx + dy*dy) + dz*dz, every step rounded, no contraction;
+ *      ties to the smaller major index; fine_nn[i] is chunk-local; fine_dist[i] = the correctly rounded sqrt;
+ *      fine_label[i] = major_label[major_off[c] + fine_nn[i]].  No radius (the reference passes max_radius=None).
+ *   F3 Ground inliers: the rules of ai_statistical_inliers on the chunk's ground rows alone, k = min(nb_neighbors, n_c).
+ *      ground_avg, mean, std and threshold are bit-equal to that entry called on the chunk by itself.
+ *   F4 Mean height.  mean_z = the float64 sum of z over the chunk's inliers divided once by their number.  Order of the sum,
+ *      with i the chunk-local index: slot s = i mod 65536 adds its inliers i = s, s + 65536, ... in ascending order; the slots
+ *      256 b .. 256 b + 255 of block b are summed as four waves of 64, each by a pairwise tree (neighbours, then pairs of 2, 4,
+ *      8, 16, 32 slots), then ((w0 + w1) + w2) + w3; the 256 block sums are summed the same way.  Without inliers mean_z is NaN
+ *      (np.mean of an empty array) and nothing is kept.
+ *   F5 Height cut.  z_limit = mean_z + mean_height, rounded once; a ground point is kept iff it is an inlier and z < z_limit
+ *      (strict).  ground_keep holds, chunk after chunk, the ascending chunk-local indices of the kept points (the reference's
+ *      [inliers][in_idcs]); chunk c's run is keep_off[c] .. keep_off[c+1].
+ *   F6 Merged chunk (the reference's pcd_chunk + cut_hight): rows merged_off[c] .. merged_off[c+1] hold chunk c's fine points in
+ *      input order, then its kept ground points in ascending order, coordinates copied bit for bit; merged_label is
+ *      fine_label + 1 for the fine part and 0 (the merge's "no instance") for the ground part.
+ *   F7 Independence.  Two calls are bit-identical, and so are a chunk's outputs whether it is finished alone, with other
+ *      chunks, or in another chunk order.
+ *   Limits and errors.  Each of the three totals is below 2^30; n_chunks <= 65535.  AI_ERR_BAD_ARG: an offset array that does
+ *      not start at 0 or decreases; a non-finite coordinate; a chunk with fine points and no major points; nb_neighbors < 1,
+ *      std_ratio <= 0, or nb_neighbors > 64 with some chunk above 64 ground points; a non-finite mean_height; fine_label or the
+ *      merged outputs without major_label; the merged outputs not all NULL or all given.  The arguments are checked in full before
+ *      any output is written.  Not errors: n_chunks == 0, an empty chunk, a chunk without ground, a chunk with one ground point
+ *      (its avg is 0: nothing is kept).
+ * Outputs, each may be NULL: fine_nn, fine_label (Nf int32), fine_dist (Nf doubles), ground_avg (Ng doubles), ground_keep
+ * (capacity Ng int32), merged_xyz (capacity (Nf + Ng) x 3), merged_label (capacity Nf + Ng) -- host or device per mem_kind, as
+ * the three point arrays and major_label are; keep_off, merged_off (n_chunks + 1 int64) and ground_stats (n_chunks x 6 doubles:
+ * mean, std, threshold, n_inliers, mean_z, z_limit; NaN statistics for a chunk without ground) are HOST arrays, as the three offset
+ * arrays are.  Two host synchronisations per call with device memory, three with host memory, whatever n_chunks is.
+ */
+int ai_chunk_finish(ai_ctx* ctx, const double* fine_xyz, const int64_t* fine_off, const double* major_xyz,
+                    const int64_t* major_off, const int32_t* major_label, const double* ground_xyz, const int64_t* ground_off,
+                    int32_t n_chunks, int32_t nb_neighbors, double std_ratio, double mean_height, int mem_kind, int32_t* fine_nn,
+                    double* fine_dist, int32_t* fine_label, double* ground_avg, int32_t* ground_keep, int64_t* keep_off,
+                    double* ground_stats, double* merged_xyz, int32_t* merged_label, int64_t* merged_off);
+
+/*
  * Timing hook for bench.py: runs `reps` fused Lanczos SpMV steps on the whole graph as
  * one segment and returns the average kernel time (HIP events on the context's stream)
  * plus the algorithmic byte count of one launch.
