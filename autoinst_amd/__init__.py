@@ -12,7 +12,7 @@ def __getattr__(name):
                 "Context", "DeviceGraph", "default_context", "last_stats", "fiedler", "sweep", "lsym_apply", "bench_spmv", "eigs_smallest"):
         from . import ncuts_api as _n
         return getattr(_n, name)
-    if name in ("Metrics", "score", "label_pairs", "merge_chunks_unite_instances2", "merge_associate", "unique_points"):
+    if name in ("Metrics", "score", "label_pairs", "merge_chunks_unite_instances2", "merge_associate", "unique_points", "merge_map"):
         from . import labels_api as _l
         return getattr(_l, name)
     if name in ("box_select", "statistical_inlier_indices", "voxel_down_sample", "chunks_from_pointcloud",

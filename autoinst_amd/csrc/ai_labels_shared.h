@@ -1,0 +1,135 @@
+// What the label bookkeeping (ai_labels.hip) and the whole-map merge (ai_merge.hip) share: the order-preserving integer forms of a
+// float64, the stable radix-sort / scan wrappers, and the kernels both use unchanged (first-occurrence flags of ai_unique_points;
+// boxes, distinct (value, tag) entries and the common-scalar walk of ai_merge_associate).  Everything has internal linkage.
+#pragma once
+#include <cstring>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "ai_common.h"
+
+namespace {
+
+template <typename T>
+int to_device(const T* src, size_t count, int mem_kind, DevBuf<T>& own, const T** dev, hipStream_t st) {
+  if (mem_kind == AI_MEM_DEVICE) {
+    *dev = src;
+    return AI_OK;
+  }
+  AI_TRY(own.alloc(count));
+  AI_HIP(hipMemcpyAsync(own.p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
+  *dev = own.p;
+  return AI_OK;
+}
+
+inline unsigned grid_for(int64_t n) { return (unsigned)((n + AI_BLOCK - 1) / AI_BLOCK); }
+
+// float64 -> uint64 with the same order (and -0.0 == +0.0, as np.unique compares values)
+__device__ __forceinline__ uint64_t ordered_bits(double v) {
+  if (v == 0.0) v = 0.0;
+  const uint64_t b = (uint64_t)__double_as_longlong(v);
+  return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double from_ordered_bits(uint64_t k) {
+  const uint64_t b = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
+  return __longlong_as_double((long long)b);
+}
+
+template <typename K>
+__global__ __launch_bounds__(AI_BLOCK) void kl_heads(const K* __restrict__ key, int64_t n, int32_t* __restrict__ head) {
+  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  head[i] = (i == 0 || key[i] != key[i - 1]) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(AI_BLOCK) void km_box_init(unsigned long long* __restrict__ box, int32_t n_inst) {
+  const int i = blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (i >= n_inst * 6) return;
+  box[i] = (i % 6 < 3) ? ~0ull : 0ull;
+}
+
+__global__ __launch_bounds__(AI_BLOCK) void km_val_tag_heads(const uint64_t* __restrict__ val, const uint32_t* __restrict__ tag, int64_t n,
+                                                             int32_t* __restrict__ head) {
+  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  head[i] = (i == 0 || val[i] != val[i - 1] || tag[i] != tag[i - 1]) ? 1 : 0;
+}
+
+// distinct (value, instance) entries, compacted; every entry counts one distinct scalar of its instance
+__global__ __launch_bounds__(AI_BLOCK) void km_distinct(const uint64_t* __restrict__ val, const uint32_t* __restrict__ tag,
+                                                        const int32_t* __restrict__ pos, int64_t n, uint64_t* __restrict__ dval,
+                                                        uint32_t* __restrict__ dtag, int32_t* __restrict__ nscal1,
+                                                        int32_t* __restrict__ nscal2) {
+  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  if (pos[i + 1] == pos[i]) return;
+  const uint32_t t = tag[i];
+  dval[pos[i]] = val[i];
+  dtag[pos[i]] = t;
+  atomicAdd((t >> 31) ? &nscal2[t & 0x7fffffffu] : &nscal1[t], 1);
+}
+
+// a value's entries are sorted side 0 first; every side-0 entry walks to the value's side-1 entries
+__global__ __launch_bounds__(AI_BLOCK) void km_common(const uint64_t* __restrict__ dval, const uint32_t* __restrict__ dtag, int64_t nd,
+                                                      int32_t n2, int32_t* __restrict__ common) {
+  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (i >= nd) return;
+  const uint32_t t = dtag[i];
+  if (t >> 31) return;
+  const uint64_t v = dval[i];
+  for (int64_t j = i + 1; j < nd && dval[j] == v; ++j) {
+    const uint32_t u = dtag[j];
+    if (u >> 31) atomicAdd(&common[(size_t)t * n2 + (u & 0x7fffffffu)], 1);
+  }
+}
+
+// open3d keys an unordered_map on the Eigen vector: equality by value and std::hash<double>, which maps
+// -0.0 and +0.0 to the same bucket; every other pair of distinct bit patterns is a distinct point
+__device__ __forceinline__ uint64_t value_bits(double v) {
+  if (v == 0.0) v = 0.0;
+  return (uint64_t)__double_as_longlong(v);
+}
+
+__global__ __launch_bounds__(AI_BLOCK) void ku_axis_keys(const double* __restrict__ xyz, const int32_t* __restrict__ order, int64_t n,
+                                                         int axis, uint64_t* __restrict__ key) {
+  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const int64_t p = order ? order[i] : i;
+  key[i] = value_bits(xyz[p * 3 + axis]);
+}
+
+__global__ __launch_bounds__(AI_BLOCK) void ku_iota(int32_t* __restrict__ a, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (i < n) a[i] = (int32_t)i;
+}
+
+__global__ __launch_bounds__(AI_BLOCK) void ku_first_flags(const double* __restrict__ xyz, const int32_t* __restrict__ order, int64_t n,
+                                                           int32_t* __restrict__ keep) {
+  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const int64_t p = order[i];
+  bool first = i == 0;
+  if (!first) {
+    const int64_t q = order[i - 1];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) first |= value_bits(xyz[p * 3 + a]) != value_bits(xyz[q * 3 + a]);
+  }
+  keep[p] = first ? 1 : 0;  // stable sorts: the first of a run is the smallest original index
+}
+
+template <typename K, typename V>
+int sort_pairs(hipStream_t st, K* kin, K* kout, V* vin, V* vout, int64_t n, int bits) {
+  size_t tmp_bytes = 0;
+  AI_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, kin, kout, vin, vout, (size_t)n, 0, bits, st));
+  DevBuf<uint8_t> tmp;
+  AI_TRY(tmp.alloc(tmp_bytes));
+  AI_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, kin, kout, vin, vout, (size_t)n, 0, bits, st));
+  return AI_OK;
+}
+
+int scan_flags(hipStream_t st, int32_t* flag_to_pos, int64_t n, DevBuf<int32_t>& tmp) {
+  AI_TRY(tmp.alloc(ai_scan_tmp_elems(n)));
+  return ai_exclusive_scan_i32(st, flag_to_pos, flag_to_pos, n, tmp.p);
+}
+
+}  // namespace

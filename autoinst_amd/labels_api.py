@@ -11,6 +11,9 @@ that results are bit-equal:
   ``calculate_full_stats:315-340``) and ``pipeline/metrics/modified_LSTQ.py:23-80``;
 * `merge_chunks_unite_instances2` -- ``pipeline/utils/point_cloud/point_cloud_utils.py:387-491``.
 
+`merge_map` is the same merge for a whole map in one resident device call (``csrc/ai_merge.hip``, rules M1-M10 of
+``include/autoinst_hip.h``), with the instance id as the identity instead of the colour.
+
 There is no CPU fallback: every function raises when the HIP library or a gfx950 device is missing.
 """
 from __future__ import annotations
@@ -292,3 +295,93 @@ def merge_chunks_unite_instances2(chunks, icp=False, *, ctx: Context | None = No
         keep = unique_points(merge_p, ctx=ctx)                                                # :489
         merge_p, merge_c = merge_p[keep], merge_c[keep]
     return merge_p, merge_c
+
+
+MERGE_STATS = ("cropped_points", "map_instances", "pairs", "relabelled")   # ai_merge_map's stats, per chunk
+
+
+def merge_map(points, instances, *, centers=None, side_length=40.0, iou_min=0.01, return_table=False, return_stats=False,
+              ctx: Context | None = None):
+    """``merge_chunks_unite_instances2`` for all chunks of a map in one device call (``ai_merge_map``, rules M1-M10 in
+    ``include/autoinst_hip.h``), the instance id being the identity: ``(points, instance, source)``.
+
+    ``points`` / ``instances``: one (n, 3) float64 array or device tensor and one integer id per point and chunk; ids are
+    chunk-local, 0 is "no instance" (`points_api.finish_chunks`' ``merged_points`` / ``merged_instance``).  ``centers``: one crop
+    centre per chunk, or ``None`` for the chunk means (M4).  Returns the merged points (first occurrences of the concatenation, in
+    order), their int32 global instance id (local id ``l`` of chunk ``c`` starts as ``sum(max id of chunks < c) + l`` and takes the
+    id of the map instance it was united with) and ``source`` (int64): the position of every merged point in the concatenation, so
+    that ``cat(per_chunk_values)[source]`` carries any per-point value -- ground-truth labels for one -- into the merged map's
+    order.  With ``return_table`` a fourth value, a list with one int32 array per chunk: entry ``l`` is the global id local id
+    ``l`` ended with; with ``return_stats`` a last value, an (n_chunks, 4) int64 array (`MERGE_STATS`).  Device tensors in give
+    device tensors out; only counts cross to the host.  Errors of M10 raise ``ValueError``."""
+    from .points_api import _concat, _is_device_tensor
+    ctx = ctx or default_context()
+    if not isinstance(points, (list, tuple)) or not isinstance(instances, (list, tuple)) or len(points) != len(instances):
+        raise ValueError("merge_map: points and instances must be lists with one entry per chunk")
+    n = len(points)
+    dev = any(_is_device_tensor(a) for a in list(points) + list(instances))
+    device = next(a.device for a in list(points) + list(instances) if _is_device_tensor(a)) if dev else None
+    xyz, off = _concat(list(points), 3, np.float64, "points", dev, device)
+    m = int(off[-1])
+    parts = []
+    for c, a in enumerate(instances):
+        if _is_device_tensor(a):
+            a = a.reshape(-1)
+            if a.is_floating_point():
+                raise ValueError(f"merge_map: instances[{c}] must be integers")
+        else:
+            a = np.asarray(a).reshape(-1)
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"merge_map: instances[{c}] must be integers")
+            if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise ValueError(f"merge_map: instances[{c}] does not fit in int32")
+        if int(a.shape[0]) != int(off[c + 1] - off[c]):
+            raise ValueError(f"merge_map: instances[{c}] has {int(a.shape[0])} entries for {int(off[c + 1] - off[c])} points")
+        parts.append(a)
+    cen = None
+    if centers is not None:
+        cen = np.ascontiguousarray(centers, dtype=np.float64)
+        if cen.shape != (n, 3):
+            raise ValueError("merge_map: centers must be (n_chunks, 3)")
+    if dev:
+        import torch
+        parts = [a.to(device=device, dtype=torch.int32) if _is_device_tensor(a) else
+                 torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=device) for a in parts]
+        inst = torch.cat(parts).contiguous() if m else torch.zeros(0, dtype=torch.int32, device=device)
+        xyz = xyz.contiguous()
+        nmax = [int(a.max()) if a.numel() else 0 for a in parts] if return_table else None
+        out_p = torch.empty((max(m, 1), 3), dtype=torch.float64, device=device)
+        out_i = torch.empty(max(m, 1), dtype=torch.int32, device=device)
+        out_s = torch.empty(max(m, 1), dtype=torch.int64, device=device)
+        torch.cuda.current_stream(device).synchronize()   # the concatenations ran on torch's stream, the library reads on its own
+        mem = _ffi.AI_MEM_DEVICE
+
+        def ptr(a):
+            return _ffi.C.c_void_p(a.data_ptr()) if a.numel() else None
+    else:
+        inst = np.ascontiguousarray(np.concatenate(parts), dtype=np.int32) if n else np.zeros(0, dtype=np.int32)
+        nmax = [int(a.max()) if a.size else 0 for a in parts] if return_table else None
+        out_p, out_i, out_s = np.empty((max(m, 1), 3)), np.empty(max(m, 1), np.int32), np.empty(max(m, 1), np.int64)
+        mem = _ffi.AI_MEM_HOST
+
+        def ptr(a):
+            return a.ctypes.data if a.size else None
+    table = stats = None
+    if return_table:
+        goff = np.concatenate([[0], np.cumsum(np.maximum(nmax, 0), dtype=np.int64)]).astype(np.int64)
+        table = np.zeros(int(goff[-1]) + 1, dtype=np.int32)
+    if return_stats:
+        stats = np.zeros((n, len(MERGE_STATS)), dtype=np.int64)
+    n_out = _ffi.C.c_int64(0)
+    out_ptr = (lambda a: _ffi.C.c_void_p(a.data_ptr())) if dev else (lambda a: a.ctypes.data)
+    _ffi.check(_ffi.load().ai_merge_map(
+        ctx._h, ptr(xyz), ptr(inst), off.ctypes.data, n, cen.ctypes.data if cen is not None else None, float(side_length),
+        float(iou_min), mem, out_ptr(out_p), out_ptr(out_i), out_ptr(out_s), _ffi.C.byref(n_out),
+        table.ctypes.data if table is not None else None, stats.ctypes.data if stats is not None else None, None), "ai_merge_map")
+    k = int(n_out.value)
+    res = [out_p[:k], out_i[:k], out_s[:k]]
+    if return_table:
+        res.append([np.concatenate([[0], table[goff[c] + 1:goff[c + 1] + 1]]).astype(np.int32) for c in range(n)])
+    if return_stats:
+        res.append(stats)
+    return tuple(res)

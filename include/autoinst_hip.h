@@ -470,6 +470,51 @@ int ai_chunk_finish(ai_ctx* ctx, const double* fine_xyz, const int64_t* fine_off
                     double* ground_stats, double* merged_xyz, int32_t* merged_label, int64_t* merged_off);
 
 /*
+ * The step that turns the chunks into the map, merge_chunks_unite_instances2 (pipeline/utils/point_cloud/point_cloud_utils.py:387-491),
+ * for all chunks of a map in one resident call.  The identity of an instance is its id, not a colour.
+ * xyz: (M, 3) float64, all chunks one after the other; inst: M int32 chunk-local instance ids, 0 = no instance (street); chunk c
+ * is rows a = off[c] .. b = off[c+1] (off: HOST, n_chunks + 1 entries).  Chunks are taken in order.
+ *   M1  Ids.  nloc[c] = the largest local id of chunk c, goff = its exclusive prefix sum.  The provisional global id of local id
+ *       l > 0 of chunk c is goff[c] + l; 0 stays 0.  Global ids are not compacted.
+ *   M2  Duplicates.  Two points are the same if all three coordinates are equal as values (-0.0 == +0.0, ai_unique_points' rule).
+ *       keep[i] is true for the first point of every distinct triple over the whole concatenation; the output is exactly the kept
+ *       points in ascending position.  A kept point has the global id its own chunk's step gave it; it never changes afterwards.
+ *       With n_chunks == 1 every point is kept, duplicates too (the reference's loop, which removes them, does not run).
+ *   M3  The map a step sees.  Step c >= 1 sees the kept points at positions < a whose global id is > 0; step 1 alone sees every
+ *       point of chunk 0, kept or not (the reference removes duplicates only at the end of its first iteration).  An empty chunk
+ *       is skipped: it associates nothing and adds nothing.
+ *   M4  Centre.  centers[c] if given; otherwise per axis the sum of the chunk's coordinates divided once by their number, the sum in
+ *       F4's order (ai_chunk_finish above) over the chunk-local row index: 65536 slots, 256 blocks of four waves, pairwise trees,
+ *       the 256 block sums the same way.  Bit-identical from call to call and independent of the other chunks of the call.
+ *   M5  Crop.  A map point of M3 is cropped in iff centre - side_length / 2 <= p <= centre + side_length / 2 on all axes, both
+ *       sides inclusive, the bounds computed as written.
+ *   M6  Per map instance g present in the crop: its box is the min and max per axis of its cropped points; S1(g) is the set of
+ *       distinct scalar coordinate values of its cropped points, the three axes pooled (np.unique without axis).
+ *   M7  Per local instance l > 0 of the chunk: S2(l) is the same set over ALL chunk points of l, duplicates and already-known
+ *       points included.
+ *   M8  Pair.  inter(g, l) = the number of chunk points of l with box_min <= p <= box_max of g; only inter > 0 counts.
+ *       union = |S1| + |S2| - |S1 n S2|; iou = double(inter) / double(union); the pair qualifies iff iou > iou_min, strictly.
+ *   M9  Association.  l takes the global id of the qualifying g with the largest iou, among equal iou the smallest g (the
+ *       order-free form of :465-477).  Several l may take the same g; an l without a qualifying pair keeps its provisional id.
+ *   M10 Limits and errors.  M < 2^30, n_chunks <= 65535, goff[n_chunks] < 2^31 - 1.  AI_ERR_BAD_ARG, with the chunk named: offsets
+ *       that do not start at 0 or that decrease; a negative local id; a non-finite coordinate; a non-finite centre;
+ *       side_length <= 0; iou_min not finite; n_out == NULL (the one output the others cannot be returned without).  Per step at
+ *       most 3 * (cropped + chunk points of instances) <= 2^31 - 2 scalar entries and (instances in the crop) x (nloc[c] + 1)
+ *       < 2^28 table entries; a step beyond either is AI_ERR_BAD_ARG.  n_chunks == 0 or M == 0 gives *n_out = 0.
+ * Outputs of capacity M, host or device per mem_kind as xyz and inst are, each may be NULL: out_xyz (n_out x 3, coordinates bit for
+ * bit), out_inst (int32 global ids), out_src (int64, the position of each kept point in the concatenation, ascending).  HOST
+ * outputs: *n_out; inst_table (goff[n_chunks] + 1 int32, may be NULL): the global id local id l of chunk c ended with at
+ * [goff[c] + l], entry 0 is 0 -- size it as 1 + the sum over the chunks of their largest id; stats (n_chunks x 4 int64, may be NULL):
+ * cropped map points, map instances present in the crop, pairs above iou_min, local instances re-labelled; centers_used
+ * (n_chunks x 3 doubles, may be NULL): the centre of every chunk (NaN for an empty chunk without a given centre).
+ * Working memory and the box loop scale with the instances present in a step's crop, not with the ids of the map.  Three host
+ * synchronisations per step, each for one or two counts; no array of points crosses the host link with device memory.
+ */
+int ai_merge_map(ai_ctx* ctx, const double* xyz, const int32_t* inst, const int64_t* off, int32_t n_chunks, const double* centers,
+                 double side_length, double iou_min, int mem_kind, double* out_xyz, int32_t* out_inst, int64_t* out_src,
+                 int64_t* n_out, int32_t* inst_table, int64_t* stats, double* centers_used);
+
+/*
  * Timing hook for bench.py: runs `reps` fused Lanczos SpMV steps on the whole graph as
  * one segment and returns the average kernel time (HIP events on the context's stream)
  * plus the algorithmic byte count of one launch.
