@@ -847,6 +847,9 @@ extern "C" int ai_affinity_build_sam(ai_ctx* ctx, const double* xyz, int64_t n, 
 
   AI_HIPF(ctx->graphs.alloc((void**)&A->orig, (size_t)n * sizeof(int32_t)));
   AI_HIPF(ctx->graphs.alloc((void**)&A->rowptr, (size_t)(n + 1) * sizeof(int32_t)));
+  // the graph keeps its points (24 bytes per point): the cut's ancestor-less segments start from their principal-axis coordinate
+  AI_HIPF(ctx->graphs.alloc((void**)&A->xyz, (size_t)n * 3 * sizeof(double)));
+  AI_HIPF(hipMemcpyAsync(A->xyz, d_xyz, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
   {
     size_t tmp_bytes = 0;
     AI_HIPF(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key.p, key2.p, idx.p, A->orig, (size_t)n, 0, 30, st));

@@ -324,6 +324,7 @@ extern "C" int ai_ctx_destroy(ai_ctx* ctx) {
       g->col = nullptr;
       g->val = nullptr;
       g->orig = nullptr;
+      g->xyz = nullptr;
       g->owner = nullptr;
     }
     ctx->live_graphs.clear();
@@ -353,6 +354,7 @@ extern "C" int ai_csr_free(ai_ctx* ctx, ai_csr* csr) {
     o->graphs.release(csr->col);
     o->graphs.release(csr->val);
     o->graphs.release(csr->orig);
+    o->graphs.release(csr->xyz);
   }
   delete csr;
   return AI_OK;

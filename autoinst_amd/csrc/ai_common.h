@@ -159,6 +159,10 @@ struct ai_csr {
   double* val;      // nnz    (device) raw affinities w_ij
   int32_t* orig;    // n      (device) internal row -> caller's original id; nullptr = identity
   int device;
+  // the caller's coordinates, 3 doubles per ORIGINAL id (device; ai_affinity_build* keeps them, nullptr: the graph was made without
+  // points): ancestor-less segments of the cut start their Lanczos solve from the principal-axis coordinate (fk_pca_*, ai_flow.inc)
+  double* xyz = nullptr;
+  const double* const* chunk_xyz = nullptr;  // (the merged view of ai_ncut_batch only) host array: xyz of each chunk of the view, in its order
   ai_ctx* owner = nullptr;  // the context whose buffer cache holds rowptr / col / val / orig; nullptr: buffers are not the handle's
                             // (a temporary view, or the owner was destroyed: then the pointers above are null as well)
 };

@@ -1,9 +1,61 @@
 // Dense symmetric eigenproblems of the projected (B x B, B <= 128) matrices of the Chebyshev-filtered subspace iteration: host
 // code, no HIP in here (tests/test_host_eigh.py compiles this header with g++ and checks one solver against the other).
+// ai_jacobi3 (the principal axis of a segment's points, fk_pca_axis) is the one routine that also runs on the device.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <vector>
+
+#ifdef __HIPCC__
+#define AI_DENSE_HD __host__ __device__
+#else
+#define AI_DENSE_HD
+#endif
+
+// Leading eigenpair of the symmetric 3 x 3 matrix a = {xx, xy, xz, yy, yz, zz} by the cyclic Jacobi sweep of cf_jacobi below: returns the
+// largest eigenvalue, e = its unit eigenvector.  SIGN: the component of e that is largest in magnitude (the first such) is positive.
+// Equal eigenvalues (a sphere, a = 0): the one met first in the order x, y, z.
+AI_DENSE_HD inline double ai_jacobi3(const double a6[6], double e[3]) {
+  double a[3][3] = {{a6[0], a6[1], a6[2]}, {a6[1], a6[3], a6[4]}, {a6[2], a6[4], a6[5]}};
+  double q[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
+    const double diag = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2];
+    if (!(off > 1e-32 * fmax(diag, 1e-300))) break;
+    for (int p = 0; p < 2; ++p)
+      for (int r = p + 1; r < 3; ++r) {
+        const double apr = a[p][r];
+        if (fabs(apr) < 1e-300) continue;
+        const double tau = (a[r][r] - a[p][p]) / (2.0 * apr);
+        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+        const double c = 1.0 / sqrt(1.0 + t * t), s = t * c;
+        for (int k = 0; k < 3; ++k) {  // columns p, r
+          const double akp = a[k][p], akr = a[k][r];
+          a[k][p] = c * akp - s * akr;
+          a[k][r] = s * akp + c * akr;
+        }
+        for (int k = 0; k < 3; ++k) {  // rows p, r
+          const double apk = a[p][k], ark = a[r][k];
+          a[p][k] = c * apk - s * ark;
+          a[r][k] = s * apk + c * ark;
+        }
+        for (int k = 0; k < 3; ++k) {
+          const double qkp = q[k][p], qkr = q[k][r];
+          q[k][p] = c * qkp - s * qkr;
+          q[k][r] = s * qkp + c * qkr;
+        }
+      }
+  }
+  int j = 0;
+  if (a[1][1] > a[j][j]) j = 1;
+  if (a[2][2] > a[j][j]) j = 2;
+  int big = 0;
+  if (fabs(q[1][j]) > fabs(q[big][j])) big = 1;
+  if (fabs(q[2][j]) > fabs(q[big][j])) big = 2;
+  const double sg = q[big][j] < 0.0 ? -1.0 : 1.0;
+  for (int k = 0; k < 3; ++k) e[k] = sg * q[k][j];
+  return a[j][j];
+}
 
 // cyclic Jacobi: eigenvalues (descending) and eigenvectors (columns of q, row-major) of the symmetric a
 inline void cf_jacobi(std::vector<double> a, int B, std::vector<double>& evals, std::vector<double>& q) {

@@ -58,6 +58,7 @@ struct FSeg {  // host record of a live segment
   bool binary_child = false;  // child of a Fiedler cut (or a root): its connectivity is not known yet
   int vdelta = 0;             // slab row of position 0 of its chunk
   int warm_n = 0;             // (warm start) rows of the last SOLVED ancestor, whose second Ritz vector lies at this segment's positions in warm[]; 0: none
+  int pca = 0;                // (principal-axis start) 1 + chunk while the segment is prepared without a solved ancestor and its graph kept its points; 0: not
   int restarts = 0;           // times the segment was solved again because its Ritz pair failed the true-residual test
   double prev_true = 0.0;     // the true residual that sent it back
 };
@@ -113,6 +114,14 @@ class Flow {
   // 105 -> 97 ms, the same partitions on every fixture of the GPU suite (DESIGN_EXPERIMENTS G1, G8).  AI_FLOW_WARM=0 is the hash start
   // of rounds 1-4 (a variant selector, read per call: tests/test_gpu_parity.py compares the two).
   int warm = (getenv("AI_FLOW_WARM") && atoi(getenv("AI_FLOW_WARM")) == 0) ? 0 : 1;
+  // A segment WITHOUT a solved ancestor (the components a chunk falls into first: 55 % of the headline chunk's row-steps) starts from
+  // u1 * (its points' coordinate along their principal axis) where the graph kept its points (fk_pca_* in ai_flow_kernels.inc; CPU
+  // study tests/tools/root_start_study.py: 0.956 of the row-steps, the same partitions; DESIGN_EXPERIMENTS G10).  Part of the warm
+  // start: AI_FLOW_WARM=0 is the pure hash start for these segments too.
+  std::vector<const double*> h_xyz;   // per chunk: its points by original id (device), nullptr: none
+  bool any_xyz = false;
+  DevBuf<const double*> d_xyz;
+  DevBuf<double> pca_part, pca_axis;  // FK_PCA_VALS planes of partials at the stable coarse indices; {axis, centre, scale} per record of a wave
   DevBuf<uint8_t> bin;
   DevBuf<int32_t> flag, fscan, map, newcnt, nscan, parent, rcnt, rc, ord, key, key_out, val, sorted_rows, final_order, scantmp;
   DevBuf<uint8_t> sorttmp;
@@ -328,7 +337,8 @@ class Flow {
       r.aux = s.aux;
       r.vdelta = s.vdelta;
       r.pad0 = s.warm_n;
-      r.pad1 = r.pad2 = 0;
+      r.pad1 = s.pca;
+      r.pad2 = 0;
       out[i] = r;
       nf += fk_nf(s.n);
       nc += fk_nc(s.n);
@@ -387,6 +397,17 @@ class Flow {
     if (warm) {
       AI_TRY(ev2.alloc(n));
       AI_TRY(warmv.alloc(n));
+      h_xyz.assign((size_t)nchunks, nullptr);
+      for (int c = 0; c < nchunks; ++c) {
+        h_xyz[c] = A->chunk_xyz ? A->chunk_xyz[c] : (nchunks == 1 ? (const double*)A->xyz : nullptr);
+        any_xyz |= h_xyz[c] != nullptr;
+      }
+      if (any_xyz) {
+        AI_TRY(d_xyz.alloc((size_t)nchunks));
+        AI_TRY(pca_part.alloc((size_t)FK_PCA_VALS * CCAP));
+        AI_TRY(pca_axis.alloc((size_t)8 * WCAP));
+        AI_HIP(hipMemcpyAsync(d_xyz.p, h_xyz.data(), (size_t)nchunks * sizeof(const double*), hipMemcpyHostToDevice, sm));
+      }
     }
     AI_TRY(bin.alloc(n));
     AI_TRY(flag.alloc(n + 1));
@@ -1380,6 +1401,11 @@ class Flow {
         w_nbin = std::min(w_nbin, (int)take);
       }
     }
+    bool any_pca = false;
+    for (FSeg& s : wC) {
+      s.pca = (any_xyz && s.warm_n == 0 && h_xyz[s.chunk]) ? s.chunk + 1 : 0;
+      any_pca |= s.pca != 0;
+    }
     if (!wC.empty()) {
       int nfC = 0, ncC = 0;
       AI_TRY(expand(wC, wrecC, fineC.p, coarseC.p, 1, nfC, ncC));
@@ -1416,6 +1442,17 @@ class Flow {
       hipLaunchKernelGGL(fk_reset_slots, dim3(((unsigned)wC.size() + AI_BLOCK - 1) / AI_BLOCK), dim3(AI_BLOCK), 0, sw, (const SegRec*)wrecC.p,
                          (int)wC.size(), L, s_lastm.p, s_nextm.p, opt.check_every, s_theta.p, s_resid.p, gate, w_nbin, (int32_t*)(pin_res() + 64));
       AI_KERNEL_CHECK();
+      if (any_pca) {  // ancestor-less segments: warm[] = u1 * principal-axis coordinate, SegRec.pad0 = their own row count
+        hipLaunchKernelGGL(fk_pca_moments, dim3(ncC), dim3(AI_BLOCK), 0, sw, (const Task*)coarseC.p, (const SegRec*)wrecC.p, G,
+                           (const double* const*)d_xyz.p, pca_part.p, (size_t)CCAP, gate, w_nbin);
+        AI_KERNEL_CHECK();
+        hipLaunchKernelGGL(fk_pca_axis, dim3((unsigned)wC.size()), dim3(AI_BLOCK), 0, sw, wrecC.p, G, (const double* const*)d_xyz.p,
+                           (const double*)pca_part.p, (size_t)CCAP, pca_axis.p, gate, w_nbin);
+        AI_KERNEL_CHECK();
+        hipLaunchKernelGGL(fk_pca_fill, dim3(ncC), dim3(AI_BLOCK), 0, sw, (const Task*)coarseC.p, (const SegRec*)wrecC.p, G,
+                           (const double* const*)d_xyz.p, (const double*)pca_axis.p, (const double*)u1.p, warmv.p, gate, w_nbin);
+        AI_KERNEL_CHECK();
+      }
       hipLaunchKernelGGL(fk_lz_init, dim3(ncC), dim3(AI_BLOCK), 0, sw, (const Task*)coarseC.p, (const SegRec*)wrecC.p, G, (const double*)u1.p, slabs[0],
                          pB0.p, cactive.p, gate, w_nbin, warm ? (const double*)warmv.p : (const double*)nullptr);
       AI_KERNEL_CHECK();

@@ -39,7 +39,9 @@ struct __attribute__((aligned(16))) SegRec {
   int32_t idx;         // index of the record in its list (wave-local segment index)
   int32_t aux;         // index of the segment in the list its per-segment inputs (volume) were computed for
   int32_t vdelta;      // row of the Lanczos vector slabs that holds position 0 of the segment's chunk (slabs cover a WINDOW of chunks)
-  int32_t pad0, pad1, pad2;
+  int32_t pad0;        // (warm start) rows of the vector that lies at the segment's positions in warm[]; 0: none (fk_lz_init)
+  int32_t pad1;        // (principal-axis start) 1 + the segment's chunk, 0: the segment does not take part (fk_pca_*)
+  int32_t pad2;
 };
 
 #define FK_NF(sr) (((sr).n + AI_FINE_ROWS - 1) / AI_FINE_ROWS)
@@ -470,11 +472,115 @@ __device__ __forceinline__ const double* fk_vec(double* const* __restrict__ slab
   return slabs[j / AI_SLAB_VECS] + (size_t)(j % AI_SLAB_VECS) * stride;
 }
 
+// ----------------------------------------------------------------------------- start vector of the ancestor-less segments
+// A segment without a solved ancestor (a component a chunk falls into first: half of a chunk's row-steps) whose graph kept its points
+// (ai_csr::xyz: ai_affinity_build*) starts from the smooth vector the points themselves give: u1 * t, t = the coordinate along the
+// principal axis of the segment's own points, centred.  Three small launches before fk_lz_init, two passes over the segment's rows:
+//   fk_pca_moments  per coarse task: the three coordinate sums and six second-moment sums of its rows about the segment's FIRST row's
+//                   point (so that they do not cancel), at the task's stable coarse index (Task.w >> 2), one plane per sum;
+//   fk_pca_axis     per segment: the partials added in task order, mean and covariance, its leading eigenvector e (ai_jacobi3: the
+//                   component of e largest in magnitude is positive), sigma = the standard deviation of t; sigma > 0 and finite:
+//                   axis[i] = {e, centre, sqrt(n) / sigma} and SegRec.pad0 = n, else pad0 stays 0 and the segment starts from the hash;
+//   fk_pca_fill     per coarse task: warm[row] = u1[row] * t[row] * sqrt(n) / sigma (root-mean-square 1 up to the correlation of degree
+//                   and coordinate), which fk_lz_init then treats like a carried warm vector of an n-row ancestor.
+// SegRec.pad1 = 1 + chunk of a segment that takes part (0: none), xyz_tab[chunk] = the chunk's points by ORIGINAL id.  The sums depend
+// on the segment's own rows and tasks only: a chunk cut in a batch gets the bits of the chunk cut alone, and a segment that is sent
+// back by the true-residual test gets the same vector again.
+#define FK_PCA_VALS 9
+__global__ __launch_bounds__(AI_BLOCK) void fk_pca_moments(const Task* __restrict__ ctasks, const SegRec* __restrict__ recs, FlowCsr G,
+                                                           const double* const* __restrict__ xyz_tab, double* __restrict__ part, size_t pstride,
+                                                           const int32_t* __restrict__ gate, int nbin) {
+  __shared__ double sm[AI_BLOCK / 64];
+  const Task tk = ctasks[blockIdx.x];
+  if (tk.z < nbin && gate[tk.z] != 1) return;
+  const SegRec sr = recs[tk.z];
+  if (sr.pad1 == 0) return;
+  const double* __restrict__ xyz = xyz_tab[sr.pad1 - 1];
+  const int32_t* __restrict__ orig = G.orig[FK_PAR(tk)];
+  const size_t o0 = (size_t)3 * (size_t)orig[sr.g0];
+  const double rx = xyz[o0], ry = xyz[o0 + 1], rz = xyz[o0 + 2];
+  double s[FK_PCA_VALS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int row = tk.x + threadIdx.x; row < tk.y; row += AI_BLOCK) {
+    const size_t o = (size_t)3 * (size_t)orig[row];
+    const double dx = xyz[o] - rx, dy = xyz[o + 1] - ry, dz = xyz[o + 2] - rz;
+    s[0] += dx;
+    s[1] += dy;
+    s[2] += dz;
+    s[3] = fma(dx, dx, s[3]);
+    s[4] = fma(dx, dy, s[4]);
+    s[5] = fma(dx, dz, s[5]);
+    s[6] = fma(dy, dy, s[6]);
+    s[7] = fma(dy, dz, s[7]);
+    s[8] = fma(dz, dz, s[8]);
+  }
+#pragma unroll
+  for (int k = 0; k < FK_PCA_VALS; ++k) {
+    const double tot = ai_block_sum(s[k], sm);
+    if (threadIdx.x == 0) part[(size_t)k * pstride + (size_t)(tk.w >> 2)] = tot;
+  }
+}
+
+// one block per record of the wave's children
+__global__ __launch_bounds__(AI_BLOCK) void fk_pca_axis(SegRec* __restrict__ recs, FlowCsr G, const double* const* __restrict__ xyz_tab,
+                                                        const double* __restrict__ part, size_t pstride, double* __restrict__ axis,
+                                                        const int32_t* __restrict__ gate, int nbin) {
+  __shared__ double sm[AI_BLOCK / 64];
+  const int i = blockIdx.x;
+  if (i < nbin && gate[i] != 1) return;
+  const SegRec sr = recs[i];
+  if (sr.pad1 == 0) return;
+  double s[FK_PCA_VALS];
+#pragma unroll
+  for (int k = 0; k < FK_PCA_VALS; ++k) s[k] = ai_range_sum(part + (size_t)k * pstride, sr.c0, sr.c0 + FK_NC(sr), sm);
+  if (threadIdx.x != 0) return;
+  const double inv = 1.0 / (double)sr.n;
+  const double mx = s[0] * inv, my = s[1] * inv, mz = s[2] * inv;
+  const double cov[6] = {s[3] * inv - mx * mx, s[4] * inv - mx * my, s[5] * inv - mx * mz,
+                         s[6] * inv - my * my, s[7] * inv - my * mz, s[8] * inv - mz * mz};
+  double e[3];
+  const double sigma = sqrt(ai_jacobi3(cov, e));
+  const double* __restrict__ xyz = xyz_tab[sr.pad1 - 1];
+  const size_t o0 = (size_t)3 * (size_t)G.orig[sr.par][sr.g0];
+  const double cx = xyz[o0] + mx, cy = xyz[o0 + 1] + my, cz = xyz[o0 + 2] + mz;
+  // every point the same (sigma = 0), or a sum that is not finite: the segment keeps the hash start
+  if (!(sigma > 0.0) || !(fabs(sigma) + fabs(cx) + fabs(cy) + fabs(cz) <= 1.7976931348623157e308)) return;
+  double* a = axis + (size_t)8 * i;
+  a[0] = e[0];
+  a[1] = e[1];
+  a[2] = e[2];
+  a[3] = cx;
+  a[4] = cy;
+  a[5] = cz;
+  a[6] = sqrt((double)sr.n) / sigma;
+  a[7] = sigma;
+  recs[i].pad0 = sr.n;
+}
+
+__global__ __launch_bounds__(AI_BLOCK) void fk_pca_fill(const Task* __restrict__ ctasks, const SegRec* __restrict__ recs, FlowCsr G,
+                                                        const double* const* __restrict__ xyz_tab, const double* __restrict__ axis,
+                                                        const double* __restrict__ u1, double* __restrict__ warm,
+                                                        const int32_t* __restrict__ gate, int nbin) {
+  const Task tk = ctasks[blockIdx.x];
+  if (tk.z < nbin && gate[tk.z] != 1) return;
+  const SegRec sr = recs[tk.z];
+  if (sr.pad1 == 0 || sr.pad0 == 0) return;
+  const double* __restrict__ xyz = xyz_tab[sr.pad1 - 1];
+  const int32_t* __restrict__ orig = G.orig[FK_PAR(tk)];
+  const double* __restrict__ a = axis + (size_t)8 * tk.z;
+  const double ex = a[0], ey = a[1], ez = a[2], cx = a[3], cy = a[4], cz = a[5], sc = a[6];
+  for (int row = tk.x + threadIdx.x; row < tk.y; row += AI_BLOCK) {
+    const size_t o = (size_t)3 * (size_t)orig[row];
+    const double t = fma(xyz[o + 2] - cz, ez, fma(xyz[o + 1] - cy, ey, (xyz[o] - cx) * ex));
+    warm[row] = (u1[row] * t) * sc;
+  }
+}
+
 // R_0 = hash(original id); partials of (R.R, u1.R) at the tasks' stable coarse indices (Task.w >> 2); flags on
 // (warm != null, round 5: a segment with a solved ancestor starts from that ancestor's SECOND Ritz vector at its own rows -- warm[],
 // carried through the partitions -- scaled to entries of order 1, plus a thousandth of the hash vector so that the start can never be
 // degenerate (CPU study: 0.1 / 0.01 / 0.001 / 0.0001 of it leave 0.931 / 0.916 / 0.908 / 0.902 of the hash start's row-steps);
-// SegRec.pad0 = the ancestor's row count, 0 = no ancestor: the hash vector alone)
+// SegRec.pad0 = the ancestor's row count, 0 = no ancestor: the hash vector alone -- unless fk_pca_axis above has set it to the segment's
+// own row count and fk_pca_fill has written warm[] at its rows)
 __global__ __launch_bounds__(AI_BLOCK) void fk_lz_init(const Task* __restrict__ ctasks, const SegRec* __restrict__ recs, FlowCsr G,
                                                        const double* __restrict__ u1, double* __restrict__ R0, double2* __restrict__ pB0,
                                                        int32_t* __restrict__ cactive, const int32_t* __restrict__ gate, int nbin,

@@ -13,6 +13,7 @@
 
 #include "ai_common.h"
 
+#include "ai_dense_sym.h"
 #include "ai_ncut_params.h"
 #include "ai_ncut_shared.h"
 #include "ai_tridiag.h"
@@ -107,9 +108,11 @@ extern "C" int ai_ncut_batch(ai_ctx* ctx, const ai_csr* const* graphs, int32_t c
   AI_TRY(vl.alloc((size_t)E));
   AI_TRY(og.alloc((size_t)N));
   std::vector<int64_t> off(count + 1, 0);
+  std::vector<const double*> chunk_xyz(count);
   int64_t eoff = 0;
   for (int c = 0; c < count; ++c) {
     const ai_csr* g = graphs[order[c]];
+    chunk_xyz[c] = g->xyz;
     norig_p[c] = num_points_orig[order[c]];
     labels_p[c] = labels_out[order[c]];
     const int64_t n = g->n, e = g->nnz;
@@ -136,6 +139,7 @@ extern "C" int ai_ncut_batch(ai_ctx* ctx, const ai_csr* const* graphs, int32_t c
   merged.val = vl.p;
   merged.orig = og.p;
   merged.device = ctx->device;
+  merged.chunk_xyz = chunk_xyz.data();
   const int rc = ncut_impl(ctx, &merged, count, off.data(), norig_p.data(), T, split_lim, opts, labels_p.data(), ngroups_p.data(), stats_out, t0);
   for (int c = 0; c < count; ++c) n_groups[order[c]] = ngroups_p[c];
   return rc;

@@ -75,7 +75,9 @@ int ai_ctx_mem_info(ai_ctx* ctx, int64_t out[4]);
  * xyz: n x 3 row-major; tarl: n x tarl_dim or NULL (theta ignored); dino likewise.
  * A falsy alpha / theta / gamma (0.0) drops that factor, as the reference's `if CONFIG[..]`.
  * gamma != 0 with dino == NULL is AI_ERR_BAD_ARG (reference raises ValueError, :126-127).
- * The graph stays on the device in the library's own (cell-sorted) row order.
+ * The graph stays on the device in the library's own (cell-sorted) row order.  It keeps a device copy of xyz (24 bytes per point,
+ * released with the graph): ai_ncut / ai_ncut_batch start the solves of segments without a solved ancestor from their points'
+ * principal-axis coordinate.  A graph made by ai_csr_from_host has no points; its segments start from the hash vector.
  */
 int ai_affinity_build(ai_ctx* ctx, const double* xyz, int64_t n,
                       const double* tarl, int32_t tarl_dim,
