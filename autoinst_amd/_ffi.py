@@ -25,6 +25,7 @@ SYMBOLS = (
     "ai_ctx_mem_info", "ai_abi_version", "ai_abi_sizeof", "ai_bench_copy",
     "ai_box_select", "ai_statistical_inliers", "ai_voxel_down_sample", "ai_camera_project",
     "ai_voxel_down_sample_nearest", "ai_scan_pool", "ai_aggregate_scans", "ai_chunk_finish", "ai_merge_map",
+    "ai_ground_planes",
 )
 ABI_VERSION = 6   # AI_ABI_VERSION of the header this binding was written against
 
@@ -120,7 +121,8 @@ def load():
                        ("ai_scan_pool", [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, dbl, C.c_int, vp, vp]),
                        ("ai_aggregate_scans", [vp, vp, vp, i32, vp, vp, vp, i32, dbl, dbl, C.c_int] + [vp] * 11 + [P(i64), P(i64)]),
                        ("ai_chunk_finish", [vp] * 8 + [i32, i32, dbl, dbl, C.c_int] + [vp] * 10),
-                       ("ai_merge_map", [vp, vp, vp, vp, i32, vp, dbl, dbl, C.c_int, vp, vp, vp, P(i64), vp, vp, vp])):
+                       ("ai_merge_map", [vp, vp, vp, vp, i32, vp, dbl, dbl, C.c_int, vp, vp, vp, P(i64), vp, vp, vp]),
+                       ("ai_ground_planes", [vp, vp, vp, i32, vp, i32, dbl, dbl, dbl, i32, C.c_uint64, i64, C.c_int] + [vp] * 5)):
         if hasattr(lib, name):   # an older build selected for an A/B run may lack them
             getattr(lib, name).argtypes = args
     if os.environ.get("AUTOINST_HIP_LIB") and not hasattr(lib, "ai_abi_version"):

@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "ai_common.h"
+#include "ai_keep.h"
 #include "ai_xform.h"
 
 namespace {
@@ -32,9 +33,7 @@ struct AGIn {
   const uint32_t* word;    // n, or null
   const uint8_t* ground;   // n, or null
   int64_t n;
-  uint32_t moving;         // A1 threshold
-  float rmin, rmax;        // A2 bounds, rounded to float32 once
-  int32_t use_moving, use_range;
+  AIKeep keep;             // A1 and A2 (ai_keep.h)
 };
 
 struct AGOut {  // index 0: ground, 1: non-ground; label and source outputs may be null
@@ -55,23 +54,13 @@ int ag_to_device(const T* src, size_t count, int mem_kind, DevBuf<T>& own, const
   return AI_OK;
 }
 
-// A1-A3 for point i: its class, coordinates and label word.  The float32 norm: s = (x*x + y*y) + z*z, every step rounded; the
-// square root is taken in float64 and rounded to float32, which is the correctly rounded float32 root (53 >= 2 * 24 + 2 bits).
-// A NaN coordinate gives a NaN r and fails both comparisons.
+// A1-A3 for point i: its class, coordinates and label word (A1 and A2 are ai_keep_point, shared with ai_ground_planes).
 __device__ __forceinline__ int ag_classify(const AGIn& a, int64_t i, float& x, float& y, float& z, uint32_t& w) {
-#pragma clang fp contract(off)
   x = a.xyz[i * 3];
   y = a.xyz[i * 3 + 1];
   z = a.xyz[i * 3 + 2];
   w = a.word ? a.word[i] : 0u;
-  bool keep = true;
-  if (a.use_moving) keep = (w & 0xFFFFu) < a.moving;
-  if (a.use_range) {
-    const float s = (x * x + y * y) + z * z;
-    const float r = (float)sqrt((double)s);
-    keep = keep && r >= a.rmin && r <= a.rmax;
-  }
-  if (!keep) return AG_DROP;
+  if (!ai_keep_point(a.keep, x, y, z, w)) return AG_DROP;
   return (a.ground && a.ground[i]) ? AG_GROUND : AG_NONGROUND;
 }
 
@@ -273,11 +262,7 @@ extern "C" int ai_aggregate_scans(ai_ctx* ctx, const float* scan_xyz, const int6
     DevBuf<int32_t> base_g, base_n, scan_tmp, b_src_g, b_src_n;
     AGIn in = {};
     in.n = M;
-    in.use_moving = use_moving ? 1 : 0;
-    in.use_range = use_range ? 1 : 0;
-    in.moving = use_moving ? (uint32_t)moving_index : 0u;
-    in.rmin = (float)range_min;
-    in.rmax = (float)range_max;
+    in.keep = ai_keep_rules(moving_index, range_min, range_max);
     AI_TRY(ag_to_device(scan_xyz, (size_t)M * 3, mem_kind, own_x, &in.xyz, st));
     if (label_word) AI_TRY(ag_to_device(label_word, (size_t)M, mem_kind, own_w, &in.word, st));
     if (ground_flag) AI_TRY(ag_to_device(ground_flag, (size_t)M, mem_kind, own_f, &in.ground, st));

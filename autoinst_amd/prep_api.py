@@ -26,9 +26,14 @@ called at ``run_pipeline.py:129``) on arrays instead of open3d clouds.
 * `aggregate_scans` / `aggregate_pointcloud` -- the head of the chain, ``aggregate_pointcloud``
   (``pipeline/utils/point_cloud/aggregate_pointcloud.py:12-188``, called at ``run_pipeline.py:102``) with the dataset's filter
   chain and label decodes: all scans of a map go to the two aggregated raw clouds in one device call (``csrc/ai_aggregate.hip``,
-  rules A1-A6 in ``include/autoinst_hip.h``).  The ground segmentation itself (Patchwork++) stays an input: per-scan masks or
-  index lists.  Not reproduced: ICP registration, open3d's RANSAC plane, and the order of the ground segmentation's index list
-  (each map is in ascending input position).
+  rules A1-A6 in ``include/autoinst_hip.h``).  Patchwork++ stays an input: per-scan masks or index lists.  Not reproduced: ICP
+  registration, the bits of open3d's unseeded RANSAC plane, and the order of the ground segmentation's index list (each map is
+  in ascending input position);
+* `ground_planes` -- the other ground segmentation of the reference, ``segment_plane(distance_threshold=0.4, ransac_n=3,
+  num_iterations=2000)`` (``aggregate_pointcloud.py:115-123``), as one seeded RANSAC plane per scan for all scans of a map in
+  one device call (``csrc/ai_ground.hip``, rules G1-G7); ``aggregate_scans(ground="ransac")`` and
+  ``aggregate_pointcloud(ground_segmentation="ransac")`` feed its flags to the aggregation on the device.  Not reproduced:
+  open3d's generator, its rmse tie-break, its early exit and its refit.
 
 All kernels are HIP (``csrc/ai_prep.hip``); there is no CPU fallback.  Inputs are NumPy arrays or float64 torch tensors
 on the context's GPU; device inputs give device outputs, so map -> major chunks -> `ncuts_api.build_affinity` /
@@ -454,8 +459,85 @@ def _widen_words(a):
     return a.to(torch.int64) & 0xFFFFFFFF
 
 
+def _range_args(range_min, range_max):
+    """(range_min, range_max) as the C entries take them: (0, -1) switches the range filter off."""
+    if range_min is None and range_max is None:
+        return 0.0, -1.0
+    rmin = 0.0 if range_min is None else float(range_min)
+    rmax = float("inf") if range_max is None else float(range_max)
+    if rmax < 0.0:
+        raise ValueError("range_max must not be negative")
+    return rmin, rmax
+
+
+GROUND_OPTIONS = ("distance_threshold", "num_iterations", "seed", "scan_base")
+
+
+def _ground_planes(ctx, xyz, off, words, moving_index, rmin, rmax, distance_threshold=0.4, num_iterations=2000, seed=0, scan_base=0,
+                   return_counts=False):
+    """``ai_ground_planes`` on prepared buffers: (flags uint8 (M,), planes, best_hyp, best_count, counts or None), where `xyz`
+    lives."""
+    n_scans, M = off.shape[0] - 1, int(xyz.shape[0])
+    n_hyp = int(num_iterations)
+    ptr, mem, torch = _call_args(xyz)
+    if torch:
+        def new(shape, dtype):
+            return torch.empty(shape, dtype=dtype, device=xyz.device)
+
+        def addr(a):
+            return C.c_void_p(a.data_ptr()) if a is not None else None
+        f64, i32, u8 = torch.float64, torch.int32, torch.uint8
+    else:
+        def new(shape, dtype):
+            return np.empty(shape, dtype=dtype)
+
+        def addr(a):
+            return a.ctypes.data if a is not None else None
+        f64, i32, u8 = np.float64, np.int32, np.uint8
+    flags, planes = new(max(M, 1), u8), new((max(n_scans, 1), 4), f64)
+    best_hyp, best_count = new(max(n_scans, 1), i32), new(max(n_scans, 1), i32)
+    counts = new((max(n_scans, 1), max(min(n_hyp, 4096), 1)), i32) if return_counts else None
+    _ffi.check(_ffi.load().ai_ground_planes(
+        ctx._h, ptr, off.ctypes.data, n_scans, addr(words), -1 if moving_index is None else int(moving_index), rmin, rmax,
+        float(distance_threshold), n_hyp, int(seed) & 0xFFFFFFFFFFFFFFFF, int(scan_base), mem, addr(flags), addr(planes), addr(best_hyp),
+        addr(best_count), addr(counts)), "ai_ground_planes")
+    return flags[:M], planes[:n_scans], best_hyp[:n_scans], best_count[:n_scans], (counts[:n_scans] if return_counts else None)
+
+
+def ground_planes(scan_points, *, labels=None, moving_index=None, range_min=None, range_max=None, distance_threshold=0.4,
+                  num_iterations=2000, seed=0, scan_base=0, scan_offsets=None, return_counts=False, ctx: Context | None = None):
+    """The ground / non-ground split of every scan in one device call (``ai_ground_planes``, rules G1-G7 in
+    ``include/autoinst_hip.h``): one RANSAC plane per scan, the ``segment_plane(distance_threshold=0.4, ransac_n=3,
+    num_iterations=2000)`` branch of ``aggregate_pointcloud`` (``aggregate_pointcloud.py:115-123``) with a counter-based sampler,
+    so that the result is a function of ``(points, seed, scan_base + scan index)`` alone.
+
+    ``scan_points``, ``labels``, ``moving_index``, ``range_min`` / ``range_max`` and ``scan_offsets`` are those of
+    `aggregate_scans`: a filtered point takes no part (never sampled, counted or flagged).  ``num_iterations`` (1 .. 4096) is the
+    number of hypotheses; every one is scored on all kept points, and the plane with the most inliers (``dist <
+    distance_threshold``, strict) wins, ties to the smallest hypothesis index.  There is no early exit and no refit.
+
+    Returns ``(flags, planes, best_hyp, best_count)``: ``flags`` one ``(M,)`` boolean array over the INPUT points (it goes
+    unchanged into ``aggregate_scans(ground=flags)``), ``planes`` ``(n_scans, 4)`` float64 ``(a, b, c, d)`` with a unit normal
+    (zeros for a scan without a plane: fewer than 3 kept points, or only degenerate samples), ``best_hyp`` int32 (-1 without a
+    plane) and ``best_count`` int32.  With ``return_counts`` also the ``(n_scans, num_iterations)`` int32 inlier counts of every
+    hypothesis (-1 for a degenerate one).  Device points give device tensors."""
+    ctx = ctx or default_context()
+    xyz, off = _scan_points(scan_points, scan_offsets)
+    words = _label_words(labels, off, xyz) if labels is not None else None
+    rmin, rmax = _range_args(range_min, range_max)
+    flags, planes, best_hyp, best_count, counts = _ground_planes(
+        ctx, xyz, off, words, moving_index, rmin, rmax, distance_threshold, num_iterations, seed, scan_base, return_counts)
+    if _is_device_tensor(flags):
+        import torch
+        flags = flags.view(torch.bool)
+    else:
+        flags = flags.view(np.bool_)
+    out = (flags, planes, best_hyp, best_count)
+    return out + (counts,) if return_counts else out
+
+
 def aggregate_scans(scan_points, poses, *, labels=None, ground=None, moving_index=None, range_min=None, range_max=None,
-                    return_source=False, scan_offsets=None, ctx: Context | None = None):
+                    return_source=False, scan_offsets=None, ground_options=None, ctx: Context | None = None):
     """All scans of a map to the two aggregated raw clouds in one device call (``ai_aggregate_scans``): the loop of
     ``aggregate_pointcloud`` (``aggregate_pointcloud.py:99-186``) with the dataset's filters (``kitti_gt_mo_filter.py:40-51``,
     ``range_filter.py:23-36``) and label decodes (``kitti_odometry_dataset.py:73-104``).
@@ -464,9 +546,11 @@ def aggregate_scans(scan_points, poses, *, labels=None, ground=None, moving_inde
     ``dataset.get_point_cloud`` returns them (column 3, the intensity, is ignored), or one float32 ``(M, 3)`` array / device
     tensor with ``scan_offsets=`` (``n_scans + 1`` entries).  ``poses``: ``(n_scans, 4, 4)``, last rows exactly ``0 0 0 1``.
     ``labels``: the raw ``.label`` words, in the same forms, uint32 or any integer dtype whose values fit.  ``ground``: per-scan
-    boolean masks or per-scan index arrays into the INPUT scan (what Patchwork++'s ``getGroundIndices`` returns), or ``None``
-    (every kept point is non-ground).  ``moving_index`` (the reference's 251) keeps a point iff ``(word & 0xFFFF) <
-    moving_index``; ``range_min`` / ``range_max`` keep it iff its float32 norm lies in ``[range_min, range_max]``, both ends
+    boolean masks or per-scan index arrays into the INPUT scan (what Patchwork++'s ``getGroundIndices`` returns), one ``(M,)``
+    mask, ``None`` (every kept point is non-ground), or ``"ransac"``: the flags of `ground_planes` with this call's own filter
+    arguments and ``ground_options`` (``distance_threshold``, ``num_iterations``, ``seed``, ``scan_base``), which stay where the
+    points are -- with device points nothing crosses to the host between the two device calls.  ``moving_index`` (the
+    reference's 251) keeps a point iff ``(word & 0xFFFF) < moving_index``; ``range_min`` / ``range_max`` keep it iff its float32 norm lies in ``[range_min, range_max]``, both ends
     inclusive; ``None`` switches a filter off (``range_min`` alone defaults the other end to 0 / infinity).
 
     Returns ``(pcd_ground, pcd_nonground, labels_dict)``: float64 ``(n, 3)`` clouds in the map frame, each in ascending input
@@ -488,14 +572,19 @@ def aggregate_scans(scan_points, poses, *, labels=None, ground=None, moving_inde
     if T.shape[0] != n_scans:
         raise ValueError(f"{T.shape[0]} poses for {n_scans} scans")
     words = _label_words(labels, off, xyz) if labels is not None else None
-    flags = _ground_flags(ground, off, xyz) if ground is not None else None
-    if range_min is None and range_max is None:
-        rmin, rmax = 0.0, -1.0
+    rmin, rmax = _range_args(range_min, range_max)
+    if isinstance(ground, str):
+        if ground != "ransac":
+            raise ValueError('ground must be None, per-scan masks or index lists, one mask, or "ransac"')
+        opts = dict(ground_options or {})
+        unknown = sorted(set(opts) - set(GROUND_OPTIONS))
+        if unknown:
+            raise ValueError(f"ground_options has no {unknown}: the options are {list(GROUND_OPTIONS)}")
+        flags = _ground_planes(ctx, xyz, off, words, moving_index, rmin, rmax, **opts)[0]   # stays where the points are
     else:
-        rmin = 0.0 if range_min is None else float(range_min)
-        rmax = float("inf") if range_max is None else float(range_max)
-        if rmax < 0.0:
-            raise ValueError("range_max must not be negative")
+        if ground_options is not None:
+            raise ValueError('ground_options goes with ground="ransac"')
+        flags = _ground_flags(ground, off, xyz) if ground is not None else None
     ptr, mem, torch = _call_args(xyz)
     cap = max(M, 1)
     if torch:
@@ -552,27 +641,33 @@ def _patchwork_segmenter():
     return segment
 
 
-def aggregate_pointcloud(dataset, ind_start, ind_end, ground_segmentation=None, icp=False, *, ctx: Context | None = None):
+def aggregate_pointcloud(dataset, ind_start, ind_end, ground_segmentation=None, icp=False, *, ground_options=None,
+                         ctx: Context | None = None):
     """Drop-in for ``aggregate_pointcloud`` (``aggregate_pointcloud.py:12``): reads ``dataset[i]`` (already filtered by the
     dataset's own chain) and ``dataset.get_pose(i)`` for ``ind_start <= i < ind_end`` and makes ONE `aggregate_scans` call with
-    the filters off.  ``ground_segmentation``: ``None``; a callable ``(points (n, 3), intensity (n,)) -> ground indices``; or
-    ``"patchwork"``, which imports ``pypatchworkpp`` (``ImportError`` when it is missing).  Returns the reference's
-    ``(map_pcd_ground, map_pcd_nonground, poses, world_pose, labels)`` with ``(n, 3)`` float64 arrays for the clouds and, per
+    the filters off.  ``ground_segmentation``: ``None``; a callable ``(points (n, 3), intensity (n,)) -> ground indices``;
+    ``"patchwork"``, which imports ``pypatchworkpp`` (``ImportError`` when it is missing); or ``"ransac"``: one seeded RANSAC
+    plane per scan on the device (`ground_planes`, options in ``ground_options``), scan key = the position in the range.
+    Returns the reference's ``(map_pcd_ground, map_pcd_nonground, poses, world_pose, labels)`` with ``(n, 3)`` float64 arrays for the clouds and, per
     key of ``labels``, the ``(n, 1)`` column that ``np.vstack`` makes of the reference's per-scan lists
     (``dataset_utils.py:193-196``); with ``ground_segmentation=None`` the 2-tuple ``(map_pcd, poses)``.
 
     ``"open3d"`` raises ``NotImplementedError``: its plane comes from open3d's RANSAC with an unseeded random generator, so there
-    is nothing to reproduce.  ``icp=True`` raises too: ICP registration is not ported.  The scan calibration correction stays
-    on the host, inside the dataset (see `aggregate_scans`)."""
+    is nothing to reproduce; ``"ransac"`` is the same search with a seeded sampler.  ``icp=True`` raises too: ICP registration
+    is not ported.  The scan calibration correction stays on the host, inside the dataset (see `aggregate_scans`)."""
     if icp:
         raise NotImplementedError("icp=True: ICP registration (open3d registration_icp against the growing map) is not ported")
     if isinstance(ground_segmentation, str):
         if ground_segmentation == "open3d":
             raise NotImplementedError('ground_segmentation="open3d" is a RANSAC plane from an unseeded random generator: '
-                                      "it has no reproducible result to port")
-        if ground_segmentation != "patchwork":
-            raise ValueError('ground_segmentation must be None, "patchwork", "open3d" or a callable')
-        ground_segmentation = _patchwork_segmenter()
+                                      'it has no reproducible result to port (ground_segmentation="ransac" is the seeded one)')
+        if ground_segmentation not in ("patchwork", "ransac"):
+            raise ValueError('ground_segmentation must be None, "patchwork", "ransac", "open3d" or a callable')
+        if ground_segmentation == "patchwork":
+            ground_segmentation = _patchwork_segmenter()
+    ransac = ground_segmentation == "ransac"
+    if ground_options is not None and not ransac:
+        raise ValueError('ground_options goes with ground_segmentation="ransac"')
     scans, poses, ground = [], [], []
     cols = {k: [] for k in AGGREGATE_LABEL_KINDS}
     for i in range(ind_start, ind_end):
@@ -584,14 +679,16 @@ def aggregate_pointcloud(dataset, ind_start, ind_end, ground_segmentation=None, 
         scans.append(p32)
         poses.append(np.asarray(dataset.get_pose(i), dtype=np.float64))
         if ground_segmentation is not None:
-            ground.append(np.asarray(ground_segmentation(p32, np.asarray(entry.intensity).reshape(-1))).reshape(-1))
+            if not ransac:
+                ground.append(np.asarray(ground_segmentation(p32, np.asarray(entry.intensity).reshape(-1))).reshape(-1))
             for kind, attr in (("seg", "semantic_labels"), ("instance", "instance_labels"), ("panoptic", "panoptic_labels")):
                 cols[kind].append(np.asarray(getattr(entry, attr)).reshape(-1, 1))
     stacked = np.stack(poses) if poses else np.zeros((0, 4, 4))
     if ground_segmentation is None:
         _, map_pcd, _ = aggregate_scans(scans, stacked, ctx=ctx)
         return map_pcd, poses
-    g, ng, info = aggregate_scans(scans, stacked, ground=ground, return_source=True, ctx=ctx)
+    g, ng, info = aggregate_scans(scans, stacked, ground="ransac" if ransac else ground, ground_options=ground_options,
+                                  return_source=True, ctx=ctx)
     labels = {}
     for kind in AGGREGATE_LABEL_KINDS:
         col = np.vstack(cols[kind]) if cols[kind] else np.zeros((0, 1), dtype=np.uint32)

@@ -517,6 +517,50 @@ int ai_merge_map(ai_ctx* ctx, const double* xyz, const int32_t* inst, const int6
                  int64_t* n_out, int32_t* inst_table, int64_t* stats, double* centers_used);
 
 /*
+ * The ground / non-ground split of every scan of a map in one call: one RANSAC plane per scan, the open3d branch of
+ * aggregate_pointcloud (pipeline/utils/point_cloud/aggregate_pointcloud.py:115-123: segment_plane(distance_threshold=0.4,
+ * ransac_n=3, num_iterations=2000)) with a counter-based sampler in place of open3d's unseeded generator.
+ * The result is a function of (points, seed, scan key) alone; ground_flag goes unchanged into ai_aggregate_scans.
+ *   G1 Kept points.  The scans lie one after the other as for ai_aggregate_scans: float32 scan_xyz, HOST scan_off.  A point takes
+ *      part iff it passes rules A1 and A2 of ai_aggregate_scans, with the same arguments and the same switches-off (one shared
+ *      predicate, csrc/ai_keep.h): the reference segments dataset[i].point_cloud, which is already filtered.  A point that is not
+ *      kept is absent: never sampled, never counted, never flagged.  m = the number of kept points of the scan, ranked in ascending
+ *      input position.
+ *   G2 Sampling.  Hypothesis h (0 <= h < n_hyp <= 4096) of the scan with key k = scan_base + s draws three distinct ranks in
+ *      [0, m), all in uint64 arithmetic modulo 2^64.  Counter c = ((k*4096 + h)*4 + j); z = seed + (c+1)*0x9E3779B97F4A7C15;
+ *      z ^= z>>30; z *= 0xBF58476D1CE4E5B9; z ^= z>>27; z *= 0x94D049BB133111EB; z ^= z>>31 (splitmix64's finaliser);
+ *      draw(j, n) = ((z>>32) * n) >> 32.  r0 = draw(0, m); r1 = draw(1, m-1), incremented if r1 >= r0; r2 = draw(2, m-2), then for
+ *      each of r0, r1 in ascending order incremented if r2 >= it.  Rank r names the r-th kept point.  A scan with m < 3 has no
+ *      plane.  scan_base (>= 0, every key below 2^48) is an argument, so that a scan segmented alone with its own key gives what
+ *      it gives inside a map.
+ *   G3 Plane.  The three points are widened to float64.  e0 = p1-p0, e1 = p2-p0, n = e0 x e1 with each component as
+ *      (a*b) - (c*d); len = the correctly rounded sqrt((nx*nx + ny*ny) + nz*nz).  The hypothesis is DEGENERATE unless len > 0 &&
+ *      len < inf.  (a, b, c) = n / len, three divisions; d = -((a*x0 + b*y0) + c*z0).  Every step is rounded on its own (no
+ *      contraction).  The normal's sign is whatever comes out.
+ *   G4 Distance.  dist = |((a*x + b*y) + c*z) + d| on the widened coordinates, no contraction; a point is an inlier iff
+ *      dist < distance_threshold: the comparison is strict, and NaN fails.
+ *   G5 Choice.  A hypothesis' score is its inlier count over the scan's kept points; the best is the largest count, ties go to the
+ *      smallest h; degenerate hypotheses never win; if all are degenerate, or m < 3, the scan has no plane.  The tie rule is ours:
+ *      open3d breaks ties by an rmse and may stop early (`probability`); both depend on summation order or thread timing there
+ *      and neither is reproduced.
+ *   G6 Outputs.  ground_flag (uint8 per INPUT point, may not be NULL): 1 iff the point is kept and is an inlier of its scan's best
+ *      plane by the expression of G4, so a scan's flags sum to its best count.  plane (n_scans x 4 float64): the best plane of
+ *      G3, zeros when there is none; there is no refit (the reference discards the model).  best_hyp (int32, -1 when there is no
+ *      plane) and best_count (int32, 0 then).  hyp_count (n_scans x n_hyp int32, may be NULL): every hypothesis' count, -1 for
+ *      a degenerate one (all of them for a scan with m < 3).
+ *   G7 Determinism, limits, errors.  Counts are integers summed with integer atomics: two calls are bit-identical.
+ *      M = scan_off[n_scans] < 2^31 - 256; n_scans x n_hyp < 2^31.  AI_ERR_BAD_ARG: a distance_threshold that is not finite and
+ *      positive; n_hyp outside 1 .. 4096; a negative scan_base (or a key of 2^48 and above); an offset array that does not start
+ *      at 0 or decreases; the moving-object filter without label_word; range_min > range_max (or a NaN bound) while the range filter
+ *      is on.  The arguments are checked in full before anything is written.  Not errors: no scans, empty scans, a scan with no plane.
+ * scan_xyz, label_word and the five outputs are host or device per mem_kind; scan_off (n_scans + 1) is a HOST array.
+ */
+int ai_ground_planes(ai_ctx* ctx, const float* scan_xyz, const int64_t* scan_off, int32_t n_scans, const uint32_t* label_word,
+                     int32_t moving_index, double range_min, double range_max, double distance_threshold, int32_t n_hyp,
+                     uint64_t seed, int64_t scan_base, int mem_kind, uint8_t* ground_flag, double* plane, int32_t* best_hyp,
+                     int32_t* best_count, int32_t* hyp_count);
+
+/*
  * Timing hook for bench.py: runs `reps` fused Lanczos SpMV steps on the whole graph as
  * one segment and returns the average kernel time (HIP events on the context's stream)
  * plus the algorithmic byte count of one launch.
