@@ -242,9 +242,11 @@ __device__ __forceinline__ void knn_insert(double (&best)[K], double d2) {
 }
 
 // kq_knn_avg (ai_prep.hip) inside one chunk: one thread per ground point in the chunk's cell order, the k smallest squared distances
-// to the chunk's ground points by rings of the chunk's cells, and kq_knn_avg's stop rule -- the search ends once the k-th best
-// distance is <= r * cell.  The chunk's sorted run starts at its first row, so the thread of local position p serves the point the
-// single call's thread p serves, over the same grid and the same rows.
+// to the chunk's ground points by rings of the chunk's cells, and kq_knn_avg's stop rule, which is kp_nn1's for the k-th best (the
+// bound is derived there and in ai_prep.hip): every unvisited point is more than lb = (nearest face gap of the box of rings 0..r)
+// - 8 ulps of the axis magnitudes away, and sqrt(kth) * (1 + 8u) <= lb leaves none among the k smallest squares.  The kNN is exact,
+// so avg does not depend on the grid; the chunk still gets the single call's grid, and its sorted run starts at its first row, so
+// the thread of local position p serves the point the single call's thread p serves, over the same rows.
 template <int K>
 __global__ __launch_bounds__(AI_BLOCK) void kf_knn_avg(const FChunk* __restrict__ tab, const int32_t* __restrict__ tstart, int nch,
                                                        const double* __restrict__ X, const double* __restrict__ Y,
@@ -267,6 +269,8 @@ __global__ __launch_bounds__(AI_BLOCK) void kf_knn_avg(const FChunk* __restrict_
 #pragma unroll
   for (int j = 0; j < K; ++j) best[j] = INFINITY;
   int64_t seen = 0;
+  const double eps = 2.220446049250313e-16;
+  const double slack = 8.0 * eps * fmax(fmax(axis_mag(x, g.minx, g.cell, g.nx), axis_mag(y, g.miny, g.cell, g.ny)), axis_mag(z, g.minz, g.cell, g.nz));
   const int rmax = max(g.nx, max(g.ny, g.nz));
   for (int r = 0; r <= rmax; ++r) {
     const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1);
@@ -309,7 +313,8 @@ __global__ __launch_bounds__(AI_BLOCK) void kf_knn_avg(const FChunk* __restrict_
 #pragma unroll
       for (int j = 1; j < K; ++j)
         if (j == k - 1) kth = best[j];
-      if (sqrt(kth) <= (double)r * g.cell) break;
+      const double lb = fmin(face_gap(x, g.minx, g.cell, cx, r, g.nx), fmin(face_gap(y, g.miny, g.cell, cy, r, g.ny), face_gap(z, g.minz, g.cell, cz, r, g.nz))) - slack;
+      if (sqrt(kth) * (1.0 + 4.0 * eps) <= lb) break;
     }
   }
   double sum = 0.0;

@@ -64,7 +64,10 @@ __global__ __launch_bounds__(AI_BLOCK) void kq_bounds(const double* __restrict__
   for (int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * AI_BLOCK)
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      const double v = xyz[i * 3 + a];
+      // fmin / fmax drop a NaN: a coordinate that is not finite goes in as +inf (kp_bounds' rule, ai_cells.inc), so that
+      // bounds() sees it in the maximum
+      const double c = xyz[i * 3 + a];
+      const double v = fabs(c) < INFINITY ? c : INFINITY;
       mn[a] = fmin(mn[a], v);
       mx[a] = fmax(mx[a], v);
     }
@@ -249,10 +252,34 @@ __device__ __forceinline__ void knn_insert(double (&best)[K], double d2) {
   }
 }
 
+// kp_nn1's two helpers (ai_points.hip, where the stop rule is derived), every step rounded on its own: the distance from x to the
+// nearer face, on one axis, of the box of rings 0..r around cell c (a side without a cell left is infinitely far), and a
+// magnitude above everything that enters an index or a face on that axis.
+__device__ __forceinline__ double face_gap(double x, double mn, double cell, int c, int r, int n) {
+#pragma clang fp contract(off)
+  const double lo = (c - r - 1 >= 0) ? x - (mn + (double)(c - r) * cell) : INFINITY;
+  const double hi = (c + r + 1 <= n - 1) ? (mn + (double)(c + r + 1) * cell) - x : INFINITY;
+  return fmin(lo, hi);
+}
+
+__device__ __forceinline__ double axis_mag(double x, double mn, double cell, int n) {
+#pragma clang fp contract(off)
+  return (fabs(mn) + (double)(n + 1) * cell) + fabs(x);
+}
+
 // One thread per point (in cell order, so that a wave's queries are neighbours): the k <= K smallest squared distances to the
 // cloud (the point itself included) by rings of cells around its own cell.  Ring r is the shell of Chebyshev cell distance r: in
-// the rows (dz, dy) on the shell's faces the whole x range [cx - r, cx + r], in the other rows the cells cx - r and cx + r.  A
-// point outside rings 0..r is more than r * cell away, so the search stops once the k-th best distance is <= r * cell.
+// the rows (dz, dy) on the shell's faces the whole x range [cx - r, cx + r], in the other rows the cells cx - r and cx + r.
+// Stop rule: kp_nn1's (ai_points.hip), for the k-th best in place of the best.  kcell_of has pcell_of's three roundings (the
+// subtraction, the product, inv_cell = fl(1 / cell)), so a point outside rings 0..r, whose stored cell index is beyond c - r ..
+// c + r on some axis, may lie at most 4u * k * cell inside that face of the box of those rings (u = 2^-53); face_gap adds three
+// roundings of its own.  All of it stays below 8u * mag, and `slack` is 16u * mag = 8 ulps of mag: every unvisited point is more
+// than lb = (nearest face gap) - slack away in exact arithmetic, so its sq_dist3 (five roundings) is at least lb^2 * (1 - 5u).
+// sqrt(kth) * (1 + 8u) <= lb gives kth <= lb^2 * (1 - 11u): strictly below the square of every unvisited point.  The k smallest
+// squares seen are then the k smallest of the whole cloud, whatever the grid is.  (sqrt(kth) <= r * cell, the rule before the
+// rounding was counted, missed a point that fl(p - min) had rounded up onto a cell border when sqrt(kth) was within a few ulps
+// of r * cell: tests/prep_cases.py finds such clouds.)  The face gap is r * cell for a query on a face of its own cell and more
+// elsewhere; with no cell left on any side lb is +inf and the loop ends.
 // avg[order[p]] = (sum of the k distances in ascending order) / k.
 template <int K>
 __global__ __launch_bounds__(AI_BLOCK) void kq_knn_avg(int64_t n, int32_t k, KGrid g, const double* __restrict__ X,
@@ -269,6 +296,8 @@ __global__ __launch_bounds__(AI_BLOCK) void kq_knn_avg(int64_t n, int32_t k, KGr
 #pragma unroll
   for (int j = 0; j < K; ++j) best[j] = INFINITY;
   int64_t seen = 0;
+  const double eps = 2.220446049250313e-16;
+  const double slack = 8.0 * eps * fmax(fmax(axis_mag(x, g.minx, g.cell, g.nx), axis_mag(y, g.miny, g.cell, g.ny)), axis_mag(z, g.minz, g.cell, g.nz));
   const int rmax = max(g.nx, max(g.ny, g.nz));
   for (int r = 0; r <= rmax; ++r) {
     const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1);
@@ -311,7 +340,8 @@ __global__ __launch_bounds__(AI_BLOCK) void kq_knn_avg(int64_t n, int32_t k, KGr
 #pragma unroll
       for (int j = 1; j < K; ++j)
         if (j == k - 1) kth = best[j];
-      if (sqrt(kth) <= (double)r * g.cell) break;
+      const double lb = fmin(face_gap(x, g.minx, g.cell, cx, r, g.nx), fmin(face_gap(y, g.miny, g.cell, cy, r, g.ny), face_gap(z, g.minz, g.cell, cz, r, g.nz))) - slack;
+      if (sqrt(kth) * (1.0 + 4.0 * eps) <= lb) break;
     }
   }
   double sum = 0.0;

@@ -304,6 +304,14 @@ int ai_unique_points(ai_ctx* ctx, const double* xyz, int64_t n, int mem_kind, in
  *   avg[i] > 0 && avg[i] < mean + std_ratio * std.  keep_index (capacity n) receives the kept indices in ascending order and
  *   *n_keep their number.  avg_out (n, per mem_kind) and stats_out (HOST: mean, std, threshold) may be NULL.  nb_neighbors < 1,
  *   std_ratio <= 0, or k > 64 is AI_ERR_BAD_ARG; n = 0 keeps nothing (stats_out is not written).  Reproducible bit for bit.
+ *   The kNN is exact: the k distances of a point are the square roots of the k smallest (dx*dx + dy*dy) + dz*dz (every step
+ *   rounded, no contraction) over the whole cloud, so avg is a function of the points alone -- not of the cell list the search
+ *   runs on -- and equals a brute-force restatement bit for bit.  mean and std are fixed-order sums (tests/prep_cases.py bounds
+ *   them against the correctly rounded ones).
+ *
+ * A NaN or infinite coordinate is AI_ERR_BAD_ARG ("coordinates are not finite") in ai_statistical_inliers and in both voxel
+ *   entries, and so is a bounding box of 1e15 or more on an axis; no output array is written then.  ai_box_select takes no
+ *   bounds: such a point fails every comparison and is inside no box.
  *
  * ai_voxel_down_sample: open3d PointCloud::VoxelDownSample (dataset_utils.py:534-535): vmin = min_bound - voxel_size / 2, voxel
  *   of p = floor((p - vmin) / voxel_size), output point = sum of the voxel's points in input-index order / their count.  Output

@@ -1,12 +1,15 @@
 """GPU suite: the chunk preparation on the device (autoinst_amd.prep_api, csrc/ai_prep.hip) against the CPU restatement
 tests/prep_ref.py on a synthetic street (synth.street_map: ~1.7 M points, 5 chunks, both clouds) and on hand-made cases.
 
-Tolerances: box select, the voxel means and their trace are bit-equal; the per-point kNN averages and the threshold agree to
-rel 1e-12 (the distances are formed in another order than cKDTree's); the kept sets are equal except for points whose oracle
-avg lies within 1e-12 x threshold of the threshold -- that set is asserted empty on the fixture."""
+Tolerances: box select, the voxel means and their trace are bit-equal; against cKDTree the per-point kNN averages and the
+threshold agree to rel 1e-12 (the distances are formed in another order than cKDTree's) and the kept sets are equal except for
+points whose oracle avg lies within 1e-12 x threshold of the threshold -- that set is asserted empty on the fixture.  The kNN
+itself is exact: on the hand-made clouds the averages equal the grid-free brute force `prep_cases.knn_avg_exact` bit for bit
+(tests/test_gpu_prep_cases.py does the same at the kernel limits)."""
 import numpy as np
 import pytest
 
+import prep_cases
 import prep_ref
 from autoinst_amd import prep_api, synth
 
@@ -92,6 +95,7 @@ def test_statistical_inliers_hand_cases(nb, ctx):
     idx, avg, st = prep_api.statistical_inlier_indices(p, nb, 2.0, return_stats=True, ctx=ctx)
     ref = prep_ref.statistical_inliers(p, nb, 2.0)
     _check_inliers(idx, avg, st, ref, f"hand nb={nb}")
+    assert avg.tobytes() == prep_cases.knn_avg_exact(p, nb).tobytes()   # the exact kNN: no tolerance
     assert not np.isin(np.arange(2995, 3000), idx).any()
     if nb <= 41:
         assert np.all(avg[:41] == 0) and not np.isin(np.arange(41), idx).any()
@@ -107,6 +111,7 @@ def test_statistical_inliers_edge_cases(ctx):
     for nb in (20, 100):                                                 # nb_neighbors > n: k = n
         idx, avg, st = f(p, nb, 1.0, return_stats=True, ctx=ctx)
         _check_inliers(idx, avg, st, prep_ref.statistical_inliers(p, nb, 1.0, brute=True), f"nb={nb} > n")
+        assert avg.tobytes() == prep_cases.knn_avg_exact(p, nb).tobytes()
     for nb, r in ((0, 2.0), (-3, 2.0), (20, 0.0), (20, -1.0)):
         with pytest.raises(ValueError):
             f(p, nb, r, ctx=ctx)
