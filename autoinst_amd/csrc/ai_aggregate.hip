@@ -16,7 +16,7 @@
 // partition (A5).  Nothing here depends on the order in which blocks run.
 #include <cmath>
 
-#include "ai_common.h"
+#include "ai_entry.h"
 #include "ai_keep.h"
 #include "ai_xform.h"
 
@@ -42,18 +42,6 @@ struct AGOut {  // index 0: ground, 1: non-ground; label and source outputs may 
   int32_t *src_g, *src_n;
 };
 
-template <typename T>
-int ag_to_device(const T* src, size_t count, int mem_kind, DevBuf<T>& own, const T** dev, hipStream_t st) {
-  if (mem_kind == AI_MEM_DEVICE) {
-    *dev = src;
-    return AI_OK;
-  }
-  AI_TRY(own.alloc(count));
-  AI_HIP(hipMemcpyAsync(own.p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
-  *dev = own.p;
-  return AI_OK;
-}
-
 // A1-A3 for point i: its class, coordinates and label word (A1 and A2 are ai_keep_point, shared with ai_ground_planes).
 __device__ __forceinline__ int ag_classify(const AGIn& a, int64_t i, float& x, float& y, float& z, uint32_t& w) {
   x = a.xyz[i * 3];
@@ -62,18 +50,6 @@ __device__ __forceinline__ int ag_classify(const AGIn& a, int64_t i, float& x, f
   w = a.word ? a.word[i] : 0u;
   if (!ai_keep_point(a.keep, x, y, z, w)) return AG_DROP;
   return (a.ground && a.ground[i]) ? AG_GROUND : AG_NONGROUND;
-}
-
-// the last s in [lo, hi] with off[s] <= i (off[lo] <= i; scans without points are skipped: their successor starts at the same offset)
-__device__ __forceinline__ int32_t ag_segment_in(const int64_t* __restrict__ off, int32_t lo, int32_t hi, int64_t i) {
-  while (lo < hi) {
-    const int32_t h = (lo + hi + 1) >> 1;
-    if (off[h] <= i)
-      lo = h;
-    else
-      hi = h - 1;
-  }
-  return lo;
 }
 
 // the class counts of the points [first, last) (at most AG_TILE of them), for thread 0 of the block
@@ -136,7 +112,7 @@ __global__ __launch_bounds__(AI_BLOCK) void ka_write(AGIn a, const int64_t* __re
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t first = (int64_t)blockIdx.x * AG_TILE, last = min(first + AG_TILE, a.n);
   // the scans the tile touches (the same for the whole block): a point's scan is searched for among them only
-  const int32_t s_lo = ag_segment_in(scan_off, 0, n_scans - 1, first), s_hi = ag_segment_in(scan_off, s_lo, n_scans - 1, last - 1);
+  const int32_t s_lo = segment_in(scan_off, 0, n_scans - 1, first), s_hi = segment_in(scan_off, s_lo, n_scans - 1, last - 1);
   float x[AG_ITEMS], y[AG_ITEMS], z[AG_ITEMS];
   uint32_t w[AG_ITEMS];
   int c[AG_ITEMS];
@@ -176,7 +152,7 @@ __global__ __launch_bounds__(AI_BLOCK) void ka_write(AGIn a, const int64_t* __re
     const int32_t r = (gr ? pre_g[j] : pre_n[j]) + rank[j];
     const int32_t row = gr ? r : tot_g + r;  // < tot_g + tot_n <= AG_TILE
     const int64_t dst = (gr ? bg : bn) + r;
-    const int32_t s = ag_segment_in(scan_off, s_lo, s_hi, i);
+    const int32_t s = segment_in(scan_off, s_lo, s_hi, i);
     double ox, oy, oz;
     ai_xf(T + (int64_t)s * 16, (double)x[j], (double)y[j], (double)z[j], ox, oy, oz);
     stage[row * 3] = ox;
@@ -201,21 +177,6 @@ __global__ __launch_bounds__(AI_BLOCK) void ka_write(AGIn a, const int64_t* __re
   for (int32_t t = threadIdx.x; t < tot_n * 3; t += AI_BLOCK) dn[t] = sn[t];
 }
 
-int ag_bad(const char* what) {
-  ai_set_error("ai_aggregate_scans: %s", what);
-  return AI_ERR_BAD_ARG;
-}
-
-// a device buffer for one optional output of a host call (nothing when the caller does not want it)
-template <typename T>
-int ag_out_buf(T* host, int64_t count, DevBuf<T>& buf, T** dev) {
-  *dev = nullptr;
-  if (!host) return AI_OK;
-  AI_TRY(buf.alloc((size_t)count));
-  *dev = buf.p;
-  return AI_OK;
-}
-
 }  // namespace
 
 extern "C" int ai_aggregate_scans(ai_ctx* ctx, const float* scan_xyz, const int64_t* scan_off, int32_t n_scans, const double* pose,
@@ -225,28 +186,29 @@ extern "C" int ai_aggregate_scans(ai_ctx* ctx, const float* scan_xyz, const int6
                                   uint32_t* out_instance_nonground, uint32_t* out_panoptic_ground, uint32_t* out_panoptic_nonground,
                                   int32_t* out_src_ground, int32_t* out_src_nonground, int64_t* class_off, int64_t* n_ground,
                                   int64_t* n_nonground) {
-  if (!ctx || !scan_off || n_scans < 0 || !n_ground || !n_nonground) return ag_bad("null pointer or negative count");
-  if (mem_kind != AI_MEM_HOST && mem_kind != AI_MEM_DEVICE) return ag_bad("mem_kind must be AI_MEM_HOST or AI_MEM_DEVICE");
-  if (scan_off[0] != 0) return ag_bad("scan_off must start at 0");
+  const auto bad = [](const char* what) { return bad_arg("ai_aggregate_scans", what); };
+  if (!ctx || !scan_off || n_scans < 0 || !n_ground || !n_nonground) return bad("null pointer or negative count");
+  if (mem_kind != AI_MEM_HOST && mem_kind != AI_MEM_DEVICE) return bad("mem_kind must be AI_MEM_HOST or AI_MEM_DEVICE");
+  if (scan_off[0] != 0) return bad("scan_off must start at 0");
   for (int32_t s = 0; s < n_scans; ++s)
-    if (scan_off[s + 1] < scan_off[s]) return ag_bad("scan_off is not monotone");
+    if (scan_off[s + 1] < scan_off[s]) return bad("scan_off is not monotone");
   const int64_t M = scan_off[n_scans];
-  if (M >= ((int64_t)1 << 31) - AI_BLOCK) return ag_bad("M must be below 2^31 - 256");
-  if (n_scans > 0 && !pose) return ag_bad("null pointer");
+  if (M >= ((int64_t)1 << 31) - AI_BLOCK) return bad("M must be below 2^31 - 256");
+  if (n_scans > 0 && !pose) return bad("null pointer");
   for (int32_t s = 0; s < n_scans; ++s) {
     const double* T = pose + (size_t)s * 16;
     for (int k = 0; k < 12; ++k)
-      if (!std::isfinite(T[k])) return ag_bad("a pose is not finite");
-    if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return ag_bad("the last row of a pose must be (0, 0, 0, 1)");
+      if (!std::isfinite(T[k])) return bad("a pose is not finite");
+    if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return bad("the last row of a pose must be (0, 0, 0, 1)");
   }
   const bool use_moving = moving_index >= 0, use_range = !(range_max < 0.0);
   // (a null array of no points is an empty array: nothing below asks for an element of it)
-  if (M > 0 && use_moving && !label_word) return ag_bad("the moving-object filter needs label_word");
-  if (use_range && !(range_min <= range_max)) return ag_bad("range_min must not exceed range_max (and neither may be NaN)");
+  if (M > 0 && use_moving && !label_word) return bad("the moving-object filter needs label_word");
+  if (use_range && !(range_min <= range_max)) return bad("range_min must not exceed range_max (and neither may be NaN)");
   const bool any_label = out_seg_ground || out_seg_nonground || out_instance_ground || out_instance_nonground || out_panoptic_ground ||
                          out_panoptic_nonground;
-  if (M > 0 && !label_word && any_label) return ag_bad("label outputs need label_word");
-  if (M > 0 && (!scan_xyz || !out_xyz_ground || !out_xyz_nonground)) return ag_bad("null pointer");
+  if (M > 0 && !label_word && any_label) return bad("label outputs need label_word");
+  if (M > 0 && (!scan_xyz || !out_xyz_ground || !out_xyz_nonground)) return bad("null pointer");
 
   const size_t n_bound = (size_t)n_scans + 1;
   std::vector<int64_t> coff(2 * n_bound, 0);
@@ -263,9 +225,9 @@ extern "C" int ai_aggregate_scans(ai_ctx* ctx, const float* scan_xyz, const int6
     AGIn in = {};
     in.n = M;
     in.keep = ai_keep_rules(moving_index, range_min, range_max);
-    AI_TRY(ag_to_device(scan_xyz, (size_t)M * 3, mem_kind, own_x, &in.xyz, st));
-    if (label_word) AI_TRY(ag_to_device(label_word, (size_t)M, mem_kind, own_w, &in.word, st));
-    if (ground_flag) AI_TRY(ag_to_device(ground_flag, (size_t)M, mem_kind, own_f, &in.ground, st));
+    AI_TRY(to_device(scan_xyz, (size_t)M * 3, mem_kind, own_x, &in.xyz, st));
+    if (label_word) AI_TRY(to_device(label_word, (size_t)M, mem_kind, own_w, &in.word, st));
+    if (ground_flag) AI_TRY(to_device(ground_flag, (size_t)M, mem_kind, own_f, &in.ground, st));
     AI_TRY(d_off.alloc(n_bound));
     AI_TRY(d_coff.alloc(2 * n_bound));
     AI_TRY(d_T.alloc((size_t)n_scans * 16));
@@ -288,16 +250,16 @@ extern "C" int ai_aggregate_scans(ai_ctx* ctx, const float* scan_xyz, const int6
     AGOut o = {out_xyz_ground,      out_xyz_nonground,      out_seg_ground,      out_seg_nonground, out_instance_ground,
                out_instance_nonground, out_panoptic_ground, out_panoptic_nonground, out_src_ground,    out_src_nonground};
     if (mem_kind != AI_MEM_DEVICE) {  // the totals are known: device copies of exactly the rows that will be written
-      AI_TRY(ag_out_buf(out_xyz_ground, ng * 3, b_xyz_g, &o.xyz_g));
-      AI_TRY(ag_out_buf(out_xyz_nonground, nn * 3, b_xyz_n, &o.xyz_n));
-      AI_TRY(ag_out_buf(out_seg_ground, ng, b_seg_g, &o.seg_g));
-      AI_TRY(ag_out_buf(out_seg_nonground, nn, b_seg_n, &o.seg_n));
-      AI_TRY(ag_out_buf(out_instance_ground, ng, b_inst_g, &o.inst_g));
-      AI_TRY(ag_out_buf(out_instance_nonground, nn, b_inst_n, &o.inst_n));
-      AI_TRY(ag_out_buf(out_panoptic_ground, ng, b_pan_g, &o.pan_g));
-      AI_TRY(ag_out_buf(out_panoptic_nonground, nn, b_pan_n, &o.pan_n));
-      AI_TRY(ag_out_buf(out_src_ground, ng, b_src_g, &o.src_g));
-      AI_TRY(ag_out_buf(out_src_nonground, nn, b_src_n, &o.src_n));
+      AI_TRY(dev_out_if_wanted(out_xyz_ground, ng * 3, b_xyz_g, &o.xyz_g));
+      AI_TRY(dev_out_if_wanted(out_xyz_nonground, nn * 3, b_xyz_n, &o.xyz_n));
+      AI_TRY(dev_out_if_wanted(out_seg_ground, ng, b_seg_g, &o.seg_g));
+      AI_TRY(dev_out_if_wanted(out_seg_nonground, nn, b_seg_n, &o.seg_n));
+      AI_TRY(dev_out_if_wanted(out_instance_ground, ng, b_inst_g, &o.inst_g));
+      AI_TRY(dev_out_if_wanted(out_instance_nonground, nn, b_inst_n, &o.inst_n));
+      AI_TRY(dev_out_if_wanted(out_panoptic_ground, ng, b_pan_g, &o.pan_g));
+      AI_TRY(dev_out_if_wanted(out_panoptic_nonground, nn, b_pan_n, &o.pan_n));
+      AI_TRY(dev_out_if_wanted(out_src_ground, ng, b_src_g, &o.src_g));
+      AI_TRY(dev_out_if_wanted(out_src_nonground, nn, b_src_n, &o.src_n));
     }
     hipLaunchKernelGGL(ka_write, dim3((unsigned)nt), dim3(AI_BLOCK), 0, st, in, (const int64_t*)d_off.p, n_scans, (const double*)d_T.p,
                        (const int32_t*)base_g.p, (const int32_t*)base_n.p, o);

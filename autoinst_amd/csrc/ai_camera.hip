@@ -12,14 +12,10 @@
 #include <cmath>
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "ai_common.h"
+#include "ai_cells.inc"
 #include "ai_xform.h"  // ai_xf: the fixed-order transform (step 1)
 
 namespace {
-
-#include "ai_cells.inc"
 
 #define AI_CAM_MAX_VIEWS 64
 
@@ -335,17 +331,17 @@ extern "C" int ai_camera_project(ai_ctx* ctx, const double* query_xyz, int64_t n
     AI_HIP(hipMemcpyAsync(d_off.p, vis_off, ((size_t)n_views + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     AI_TRY(d_bits.alloc((size_t)nc));
     AI_HIP(hipMemsetAsync(d_bits.p, 0, (size_t)nc * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(kc_view_bits, dim3((unsigned)((total + AI_BLOCK - 1) / AI_BLOCK)), dim3(AI_BLOCK), 0, st, dvi, total,
+    hipLaunchKernelGGL(kc_view_bits, dim3(grid_for(total)), dim3(AI_BLOCK), 0, st, dvi, total,
                        (const int64_t*)d_off.p, (int)n_views, nc, d_bits.p, d_bad.p);
     AI_KERNEL_CHECK();
     Cells C;
     AI_TRY(build_cells(ctx, dc, nc, radius, C, who));
     AI_TRY(d_sbits.alloc((size_t)nc));
-    const unsigned gc = (unsigned)((nc + AI_BLOCK - 1) / AI_BLOCK);
+    const unsigned gc = grid_for(nc);
     hipLaunchKernelGGL(kc_gather_bits, dim3(gc), dim3(AI_BLOCK), 0, st, (const unsigned long long*)d_bits.p, (const int32_t*)C.order.p, nc,
                        d_sbits.p);
     AI_KERNEL_CHECK();
-    const unsigned gq = (unsigned)((nq * 16 + AI_BLOCK - 1) / AI_BLOCK);
+    const unsigned gq = grid_for(nq * 16);
     hipLaunchKernelGGL(kc_visible, dim3(gq), dim3(AI_BLOCK), 0, st, dq, nq, C.g, radius * radius, (const double*)C.X.p,
                        (const double*)C.Y.p, (const double*)C.Z.p, (const unsigned long long*)d_sbits.p, (const int32_t*)C.cstart.p,
                        (const int32_t*)C.cend.p, (const double*)d_T.p, all_views, max_dist, d_seen.p);

@@ -1,6 +1,16 @@
-// The uniform cell list shared by the point-cloud searches (ai_points.hip, ai_camera.hip): the squared distance of every
-// radius / nearest-point test, a dense grid of [start, end) cell ranges over points sorted by cell, and the host-to-device
-// copy of a caller's buffer.  Included inside each user's anonymous namespace (every translation unit keeps its own copy).
+// The cell lists of the point-cloud searches (ai_points.hip, ai_camera.hip, ai_scanpool.hip, ai_finish.hip, ai_prep.hip): the squared
+// distance of every radius / nearest-point test; the dense list (PGrid: [start, end) cell ranges over points sorted by cell) of the
+// radius and 1-NN searches; the row list (KGrid: points sorted by (z, y) row, x by binary search) of the kNN searches; the stop rule
+// the ring searches share, with its two helpers.  A header like any other (included at file scope, its own anonymous namespace) under
+// the file name the cell list always had.  Everything has internal linkage.
+#pragma once
+#include <climits>
+#include <cmath>
+
+#include "ai_entry.h"
+#include "ai_runs.h"
+
+namespace {
 
 // The squared distance of both searches, in the order of nanoflann's L2_Adaptor (what open3d's KDTreeFlann runs) and of
 // cdist: (dx*dx + dy*dy) + dz*dz, every product and sum rounded on its own.  The default -ffp-contract=fast would fuse the
@@ -90,6 +100,9 @@ struct Cells {
   DevBuf<double> X, Y, Z;
 };
 
+// A template only so that the 32-bit radix sort is instantiated in the sources that build a dense list, not in every source that
+// includes this header for its helpers.
+template <typename Key = uint32_t>
 int build_cells(ai_ctx* ctx, const double* d_xyz, int64_t n, double cell, Cells& C, const char* who) {
   hipStream_t st = ctx->stream;
   const int nb = 256;
@@ -126,9 +139,10 @@ int build_cells(ai_ctx* ctx, const double* d_xyz, int64_t n, double cell, Cells&
   C.g.ny = (int)floor((mx[1] - mn[1]) / cell) + 1;
   C.g.nz = (int)floor((mx[2] - mn[2]) / cell) + 1;
   const int64_t ncell = (int64_t)C.g.nx * C.g.ny * C.g.nz;
-  const unsigned gb = (unsigned)((n + AI_BLOCK - 1) / AI_BLOCK);
-  DevBuf<uint32_t> key, skey;
+  const unsigned gb = grid_for(n);
+  DevBuf<Key> key, skey;
   DevBuf<int32_t> idx;
+  DevBuf<uint8_t> tmp;
   AI_TRY(key.alloc(n));
   AI_TRY(skey.alloc(n));
   AI_TRY(idx.alloc(n));
@@ -140,13 +154,7 @@ int build_cells(ai_ctx* ctx, const double* d_xyz, int64_t n, double cell, Cells&
   AI_TRY(C.Z.alloc(n));
   hipLaunchKernelGGL(kp_keys, dim3(gb), dim3(AI_BLOCK), 0, st, d_xyz, n, C.g, key.p, idx.p);
   AI_KERNEL_CHECK();
-  int bits = 1;
-  while (((int64_t)1 << bits) < ncell) ++bits;
-  size_t tmp_bytes = 0;
-  AI_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key.p, skey.p, idx.p, C.order.p, (size_t)n, 0, bits, st));
-  DevBuf<uint8_t> tmp;
-  AI_TRY(tmp.alloc(tmp_bytes));
-  AI_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, key.p, skey.p, idx.p, C.order.p, (size_t)n, 0, bits, st));
+  AI_TRY(sort_pairs(st, key.p, skey.p, idx.p, C.order.p, n, std::max(1, bits_for(ncell)), tmp));
   AI_HIP(hipMemsetAsync(C.cstart.p, 0xff, (size_t)ncell * sizeof(int32_t), st));
   AI_HIP(hipMemsetAsync(C.cend.p, 0, (size_t)ncell * sizeof(int32_t), st));
   hipLaunchKernelGGL(kp_gather, dim3(gb), dim3(AI_BLOCK), 0, st, d_xyz, (const int32_t*)C.order.p, (const uint32_t*)skey.p, n, C.X.p, C.Y.p,
@@ -156,14 +164,80 @@ int build_cells(ai_ctx* ctx, const double* d_xyz, int64_t n, double cell, Cells&
   return AI_OK;
 }
 
-template <typename T>
-int to_device(const T* src, size_t count, int mem_kind, DevBuf<T>& own, const T** dev, hipStream_t st) {
-  if (mem_kind == AI_MEM_DEVICE) {
-    *dev = src;
-    return AI_OK;
-  }
-  AI_TRY(own.alloc(count));
-  AI_HIP(hipMemcpyAsync(own.p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
-  *dev = own.p;
-  return AI_OK;
+// ----------------------------------------------------------------------------- the stop rule of the ring searches
+// A ring search visits the cells around a query's own cell c by rings (ring r: the shell of Chebyshev cell distance r) and stops
+// when nothing unvisited can matter.  A source outside rings 0..r has, on some axis, a stored cell index k >= c + r + 1 (or
+// <= c - r - 1), so it lies beyond that face F = min + k * cell of the box of those rings -- up to the rounding of pcell_of /
+// kcell_of.  With u = 2^-53: the index is floor(fl(fl(p - min) * inv_cell)) and inv_cell = fl(1 / cell), three roundings, so
+// fl(..) >= k only gives p - min >= k * cell * (1 - 4u) (and < k * cell * (1 + 4u) on the low side; the clamp to n - 1 only lowers
+// a stored index): the source may lie 4u * k * cell inside the face.  face_gap computes |F - x| with three more roundings, of
+// k * cell, of F and of the difference: at most u * (k * cell + |F| + |F| + |x|) off.  With mag >= |min| + (n + 1) * cell + |x| on
+// every axis (axis_mag), which bounds k * cell, |F| and |x|, all of it stays below 8u * mag; `slack` is 16u * mag = 8 ulps of mag,
+// as in kn_nearest (ai_prep.hip).  So every unvisited source is more than lb = (nearest face gap) - slack away, in exact arithmetic.
+// sq_dist3 rounds five times, hence returns at least d^2 * (1 - 5u) for a source at distance d > lb; sqrt(best) * (1 + 8u) <= lb
+// gives best <= lb^2 * (1 - 11u) after the rounding of the sqrt and of the product: strictly below the square of every unvisited
+// source, so none is nearer or tied -- for the best of the 1-NN search and for the k-th best of the kNN search alike, whatever the
+// grid is.  The face gap is at least r * cell, the bound the rule had before the rounding was counted (sqrt(best) <= r * cell
+// missed a source that fl(p - min) had rounded up onto a cell border when sqrt(best) was within a few ulps of r * cell:
+// tests/points_cases.py and tests/prep_cases.py find such clouds): an extra ring is searched only when sqrt(best) is within the
+// slack of it.  With no cell left on any side lb is +inf and the loop ends.
+
+// The distances from x to the two faces, on one axis, of the box of rings 0..r around cell c: the planes min + (c - r) * cell and
+// min + (c + r + 1) * cell.  A side on which the grid has no cell left counts as infinitely far.  Every step is rounded on its own
+// (no contraction), so that the slack of the stop rule can be counted and tests/points_cases.py can restate it.
+__device__ __forceinline__ double face_gap(double x, double mn, double cell, int c, int r, int n) {
+#pragma clang fp contract(off)
+  const double lo = (c - r - 1 >= 0) ? x - (mn + (double)(c - r) * cell) : INFINITY;
+  const double hi = (c + r + 1 <= n - 1) ? (mn + (double)(c + r + 1) * cell) - x : INFINITY;
+  return fmin(lo, hi);
 }
+
+// |min| + (n + 1) * cell + |x|: above every magnitude that enters an index or a face on this axis
+__device__ __forceinline__ double axis_mag(double x, double mn, double cell, int n) {
+#pragma clang fp contract(off)
+  return (fabs(mn) + (double)(n + 1) * cell) + fabs(x);
+}
+
+// ----------------------------------------------------------------------------- the row list
+struct KGrid {
+  double minx, miny, minz, inv_cell, cell;
+  int nx, ny, nz;
+};
+
+// pcell_of's three roundings (the subtraction, the product, inv_cell = fl(1 / cell)): the stop rule counts them
+__device__ __forceinline__ void kcell_of(const KGrid& g, double x, double y, double z, int& cx, int& cy, int& cz) {
+  cx = min(max((int)floor((x - g.minx) * g.inv_cell), 0), g.nx - 1);
+  cy = min(max((int)floor((y - g.miny) * g.inv_cell), 0), g.ny - 1);
+  cz = min(max((int)floor((z - g.minz) * g.inv_cell), 0), g.nz - 1);
+}
+
+// skey = the sorted keys, row (z, y) in the high 32 bits and the x cell in the low 32: the sorted coordinates, the x cell of every
+// sorted point and the [start, end) run of every occupied row
+__global__ __launch_bounds__(AI_BLOCK) void kq_gather(const double* __restrict__ xyz, const int32_t* __restrict__ order,
+                                                      const uint64_t* __restrict__ skey, int64_t n, double* __restrict__ X,
+                                                      double* __restrict__ Y, double* __restrict__ Z, int32_t* __restrict__ scx,
+                                                      int32_t* __restrict__ rstart, int32_t* __restrict__ rend) {
+  const int64_t p = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (p >= n) return;
+  const int64_t o = order[p];
+  X[p] = xyz[o * 3];
+  Y[p] = xyz[o * 3 + 1];
+  Z[p] = xyz[o * 3 + 2];
+  const uint64_t k = skey[p];
+  scx[p] = (int32_t)(uint32_t)k;
+  const uint32_t row = (uint32_t)(k >> 32);
+  if (p == 0 || (uint32_t)(skey[p - 1] >> 32) != row) rstart[row] = (int32_t)p;
+  if (p == n - 1 || (uint32_t)(skey[p + 1] >> 32) != row) rend[row] = (int32_t)(p + 1);
+}
+
+// keep the K smallest values seen in best[0..K-1] (ascending); compile-time indices only, so the list stays in registers
+template <int K>
+__device__ __forceinline__ void knn_insert(double (&best)[K], double d2) {
+  if (d2 < best[K - 1]) {
+#pragma unroll
+    for (int j = K - 1; j > 0; --j) best[j] = d2 < best[j - 1] ? best[j - 1] : fmin(d2, best[j]);
+    best[0] = fmin(best[0], d2);
+  }
+}
+
+}  // namespace

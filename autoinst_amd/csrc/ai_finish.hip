@@ -17,18 +17,9 @@
 #include <cmath>
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "ai_common.h"
-
-namespace {
-
 #include "ai_cells.inc"
 
-struct KGrid {
-  double minx, miny, minz, inv_cell, cell;
-  int nx, ny, nz;
-};
+namespace {
 
 // one chunk: where its rows start, the cell list of its major points (1-NN) and the row list of its ground points (kNN)
 struct FChunk {
@@ -116,23 +107,9 @@ __global__ __launch_bounds__(AI_BLOCK) void kf_mkeys(const double* __restrict__ 
   idx[i] = (int32_t)i;
 }
 
-// kp_nn1's two helpers (ai_points.hip), every step rounded on its own
-__device__ __forceinline__ double face_gap(double x, double mn, double cell, int c, int r, int n) {
-#pragma clang fp contract(off)
-  const double lo = (c - r - 1 >= 0) ? x - (mn + (double)(c - r) * cell) : INFINITY;
-  const double hi = (c + r + 1 <= n - 1) ? (mn + (double)(c + r + 1) * cell) - x : INFINITY;
-  return fmin(lo, hi);
-}
-
-__device__ __forceinline__ double axis_mag(double x, double mn, double cell, int n) {
-#pragma clang fp contract(off)
-  return (fabs(mn) + (double)(n + 1) * cell) + fabs(x);
-}
-
 // One thread per fine point, a block inside one chunk: the exact nearest major point of the chunk (smallest sq_dist3, ties to the
-// smaller major row; distance = its correctly rounded sqrt) by growing rings of the chunk's cells.  The stop rule is kp_nn1's
-// (ai_points.hip, where the bound is derived): every unvisited source is more than lb = (nearest face gap of the box of rings
-// 0..r) - 8 ulps of the axis magnitudes away, and sqrt(best) * (1 + 8u) <= lb leaves none nearer or tied.
+// smaller major row; distance = its correctly rounded sqrt) by growing rings of the chunk's cells: kp_nn1's search body (ai_points.hip)
+// and the ring searches' stop rule (ai_cells.inc, where it is derived), for the best.
 __global__ __launch_bounds__(AI_BLOCK) void kf_nn1(const double* __restrict__ q, const FChunk* __restrict__ tab,
                                                    const int32_t* __restrict__ tstart, int nch, const double* __restrict__ X,
                                                    const double* __restrict__ Y, const double* __restrict__ Z,
@@ -193,12 +170,6 @@ __global__ __launch_bounds__(AI_BLOCK) void kf_nn1(const double* __restrict__ q,
 
 // ----------------------------------------------------------------------------- ground inliers (F3)
 
-__device__ __forceinline__ void kcell_of(const KGrid& g, double x, double y, double z, int& cx, int& cy, int& cz) {
-  cx = min(max((int)floor((x - g.minx) * g.inv_cell), 0), g.nx - 1);
-  cy = min(max((int)floor((y - g.miny) * g.inv_cell), 0), g.ny - 1);
-  cz = min(max((int)floor((z - g.minz) * g.inv_cell), 0), g.nz - 1);
-}
-
 // sort key: the chunk's row base + row (z, y) in the high 32 bits, the x cell in the low 32 (kq_keys with a row base)
 __global__ __launch_bounds__(AI_BLOCK) void kf_gkeys(const double* __restrict__ xyz, const FChunk* __restrict__ tab,
                                                      const int32_t* __restrict__ tstart, int nch, uint64_t* __restrict__ key,
@@ -214,39 +185,10 @@ __global__ __launch_bounds__(AI_BLOCK) void kf_gkeys(const double* __restrict__ 
   idx[i] = (int32_t)i;
 }
 
-__global__ __launch_bounds__(AI_BLOCK) void kf_ggather(const double* __restrict__ xyz, const int32_t* __restrict__ order,
-                                                       const uint64_t* __restrict__ skey, int64_t n, double* __restrict__ X,
-                                                       double* __restrict__ Y, double* __restrict__ Z, int32_t* __restrict__ scx,
-                                                       int32_t* __restrict__ rstart, int32_t* __restrict__ rend) {
-  const int64_t p = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  if (p >= n) return;
-  const int64_t o = order[p];
-  X[p] = xyz[o * 3];
-  Y[p] = xyz[o * 3 + 1];
-  Z[p] = xyz[o * 3 + 2];
-  const uint64_t k = skey[p];
-  scx[p] = (int32_t)(uint32_t)k;
-  const uint32_t row = (uint32_t)(k >> 32);
-  if (p == 0 || (uint32_t)(skey[p - 1] >> 32) != row) rstart[row] = (int32_t)p;
-  if (p == n - 1 || (uint32_t)(skey[p + 1] >> 32) != row) rend[row] = (int32_t)(p + 1);
-}
-
-// keep the K smallest values seen in best[0..K-1] (ascending); compile-time indices only, so the list stays in registers
-template <int K>
-__device__ __forceinline__ void knn_insert(double (&best)[K], double d2) {
-  if (d2 < best[K - 1]) {
-#pragma unroll
-    for (int j = K - 1; j > 0; --j) best[j] = d2 < best[j - 1] ? best[j - 1] : fmin(d2, best[j]);
-    best[0] = fmin(best[0], d2);
-  }
-}
-
 // kq_knn_avg (ai_prep.hip) inside one chunk: one thread per ground point in the chunk's cell order, the k smallest squared distances
-// to the chunk's ground points by rings of the chunk's cells, and kq_knn_avg's stop rule, which is kp_nn1's for the k-th best (the
-// bound is derived there and in ai_prep.hip): every unvisited point is more than lb = (nearest face gap of the box of rings 0..r)
-// - 8 ulps of the axis magnitudes away, and sqrt(kth) * (1 + 8u) <= lb leaves none among the k smallest squares.  The kNN is exact,
-// so avg does not depend on the grid; the chunk still gets the single call's grid, and its sorted run starts at its first row, so
-// the thread of local position p serves the point the single call's thread p serves, over the same rows.
+// to the chunk's ground points by rings of the chunk's cells: kq_knn_avg's search body and the ring searches' stop rule (ai_cells.inc,
+// where it is derived), for the k-th best.  The kNN is exact, so avg does not depend on the grid; the chunk still gets the single call's grid, and its sorted run starts at its first row,
+// so the thread of local position p serves the point the single call's thread p serves, over the same rows.
 template <int K>
 __global__ __launch_bounds__(AI_BLOCK) void kf_knn_avg(const FChunk* __restrict__ tab, const int32_t* __restrict__ tstart, int nch,
                                                        const double* __restrict__ X, const double* __restrict__ Y,
@@ -472,12 +414,6 @@ __global__ __launch_bounds__(AI_BLOCK) void kf_write_fine(const double* __restri
 
 // ----------------------------------------------------------------------------- host
 
-int bits_for(int64_t count) {  // bits that hold 0 .. count - 1
-  int b = 0;
-  while (b < 63 && ((int64_t)1 << b) < count) ++b;
-  return b;
-}
-
 int check_offsets(const int64_t* off, int32_t n, const char* name) {
   if (off[0] != 0) {
     ai_set_error("ai_chunk_finish: %s must start at 0", name);
@@ -517,22 +453,6 @@ int chunk_bounds(const double* hp, int c, double mn[3], double mx[3], const char
 void tiles_of(const int64_t* off, int32_t n, std::vector<int32_t>& t) {
   t.assign((size_t)n + 1, 0);
   for (int32_t c = 0; c < n; ++c) t[c + 1] = t[c] + (int32_t)((off[c + 1] - off[c] + AI_BLOCK - 1) / AI_BLOCK);
-}
-
-template <typename K, typename V>
-int sort_pairs(hipStream_t st, K* key, K* skey, V* val, V* sval, int64_t n, int bits, DevBuf<uint8_t>& tmp) {
-  size_t tmp_bytes = 0;
-  AI_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key, skey, val, sval, (size_t)n, 0, bits, st));
-  AI_TRY(tmp.alloc(tmp_bytes));
-  AI_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, key, skey, val, sval, (size_t)n, 0, bits, st));
-  return AI_OK;
-}
-
-template <typename T>
-int upload(const std::vector<T>& h, DevBuf<T>& d, hipStream_t st) {
-  AI_TRY(d.alloc(h.size()));
-  if (!h.empty()) AI_HIP(hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  return AI_OK;
 }
 
 }  // namespace
@@ -738,7 +658,7 @@ extern "C" int ai_chunk_finish(ai_ctx* ctx, const double* fine_xyz, const int64_
     AI_HIP(hipMemsetAsync(cend.p, 0, (size_t)ncell * sizeof(int32_t), st));
     // kp_gather (ai_cells.inc): the sorted coordinates and the [start, end) run of every occupied cell; a chunk's cells are a range of
     // their own in the table, so its runs never hold another chunk's point
-    hipLaunchKernelGGL(kp_gather, dim3((unsigned)((Nm + AI_BLOCK - 1) / AI_BLOCK)), dim3(AI_BLOCK), 0, st, dm, (const int32_t*)morder.p,
+    hipLaunchKernelGGL(kp_gather, dim3(grid_for(Nm)), dim3(AI_BLOCK), 0, st, dm, (const int32_t*)morder.p,
                        (const uint32_t*)mskey.p, Nm, MX.p, MY.p, MZ.p, cstart.p, cend.p);
     AI_KERNEL_CHECK();
     o_nn = fine_nn;
@@ -799,7 +719,7 @@ extern "C" int ai_chunk_finish(ai_ctx* ctx, const double* fine_xyz, const int64_
       AI_TRY(sort_pairs(st, gkey.p, gskey.p, gidx.p, gorder.p, Ng, 32 + std::max(1, bits_for(nrow)), sort_tmp_g));
       AI_HIP(hipMemsetAsync(rstart.p, 0, (size_t)nrow * sizeof(int32_t), st));
       AI_HIP(hipMemsetAsync(rend.p, 0, (size_t)nrow * sizeof(int32_t), st));
-      hipLaunchKernelGGL(kf_ggather, dim3((unsigned)((Ng + AI_BLOCK - 1) / AI_BLOCK)), dim3(AI_BLOCK), 0, st, dg, (const int32_t*)gorder.p,
+      hipLaunchKernelGGL(kq_gather, dim3(grid_for(Ng)), dim3(AI_BLOCK), 0, st, dg, (const int32_t*)gorder.p,
                          (const uint64_t*)gskey.p, Ng, GX.p, GY.p, GZ.p, scx.p, rstart.p, rend.p);
       AI_KERNEL_CHECK();
 #define KF_ARGS                                                                                                                     \

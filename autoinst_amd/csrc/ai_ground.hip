@@ -17,7 +17,7 @@
 // Counts are integers added with integer atomics: nothing depends on the order in which blocks run (G7).
 #include <cmath>
 
-#include "ai_common.h"
+#include "ai_entry.h"
 #include "ai_keep.h"
 
 namespace {
@@ -58,18 +58,6 @@ __device__ __forceinline__ uint64_t gr_mix(uint64_t seed, uint64_t c) {
 }
 __device__ __forceinline__ uint64_t gr_draw(uint64_t seed, uint64_t counter4, int j, uint64_t n) {
   return ((gr_mix(seed, counter4 + (uint64_t)j) >> 32) * n) >> 32;
-}
-
-// the last s in [lo, hi] with off[s] <= i (off[lo] <= i; entries without elements are skipped: their successor starts at the same offset)
-__device__ __forceinline__ int32_t gr_segment_in(const int64_t* __restrict__ off, int32_t lo, int32_t hi, int64_t i) {
-  while (lo < hi) {
-    const int32_t h = (lo + hi + 1) >> 1;
-    if (off[h] <= i)
-      lo = h;
-    else
-      hi = h - 1;
-  }
-  return lo;
 }
 
 __global__ __launch_bounds__(AI_BLOCK) void kg_keep(GRIn a, int32_t* __restrict__ kept) {
@@ -140,7 +128,7 @@ __global__ __launch_bounds__(AI_BLOCK) void kg_score(GRIn a, const int64_t* __re
                                                      int32_t* __restrict__ hyp_count) {
   __shared__ double pts[GR_SLAB * 3];
   const int64_t g = blockIdx.x;
-  const int32_t s = gr_segment_in(slab_off, 0, n_scans - 1, g);
+  const int32_t s = segment_in(slab_off, 0, n_scans - 1, g);
   const int64_t first = scan_off[s] + (g - slab_off[s]) * GR_SLAB;
   const int64_t last = min(first + (int64_t)GR_SLAB, scan_off[s + 1]);
   const int32_t cnt = (int32_t)(last - first);   // 1 .. GR_SLAB
@@ -197,10 +185,10 @@ __global__ __launch_bounds__(AI_BLOCK) void kg_flags(GRIn a, const int64_t* __re
                                                      const int32_t* __restrict__ best_hyp, const double* __restrict__ best_plane,
                                                      uint8_t* __restrict__ flag) {
   const int64_t first = (int64_t)blockIdx.x * AI_BLOCK, last = min(first + AI_BLOCK, a.n);
-  const int32_t s_lo = gr_segment_in(scan_off, 0, n_scans - 1, first), s_hi = gr_segment_in(scan_off, s_lo, n_scans - 1, last - 1);
+  const int32_t s_lo = segment_in(scan_off, 0, n_scans - 1, first), s_hi = segment_in(scan_off, s_lo, n_scans - 1, last - 1);
   const int64_t i = first + threadIdx.x;
   if (i >= last) return;
-  const int32_t s = gr_segment_in(scan_off, s_lo, s_hi, i);
+  const int32_t s = segment_in(scan_off, s_lo, s_hi, i);
   float x, y, z;
   uint8_t f = 0;
   if (gr_kept(a, i, x, y, z) && best_hyp[s] >= 0) {
@@ -210,57 +198,29 @@ __global__ __launch_bounds__(AI_BLOCK) void kg_flags(GRIn a, const int64_t* __re
   flag[i] = f;
 }
 
-int gr_bad(const char* what) {
-  ai_set_error("ai_ground_planes: %s", what);
-  return AI_ERR_BAD_ARG;
-}
-
-template <typename T>
-int gr_to_device(const T* src, size_t count, int mem_kind, DevBuf<T>& own, const T** dev, hipStream_t st) {
-  if (mem_kind == AI_MEM_DEVICE) {
-    *dev = src;
-    return AI_OK;
-  }
-  AI_TRY(own.alloc(count));
-  AI_HIP(hipMemcpyAsync(own.p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
-  *dev = own.p;
-  return AI_OK;
-}
-
-// an output of the call on the device: the caller's buffer with device memory, else a buffer of the call (copied back at the end)
-template <typename T>
-int gr_out(T* user, size_t count, int mem_kind, DevBuf<T>& own, T** dev) {
-  if (mem_kind == AI_MEM_DEVICE && user) {
-    *dev = user;
-    return AI_OK;
-  }
-  AI_TRY(own.alloc(count));
-  *dev = own.p;
-  return AI_OK;
-}
-
 }  // namespace
 
 extern "C" int ai_ground_planes(ai_ctx* ctx, const float* scan_xyz, const int64_t* scan_off, int32_t n_scans, const uint32_t* label_word,
                                 int32_t moving_index, double range_min, double range_max, double distance_threshold, int32_t n_hyp,
                                 uint64_t seed, int64_t scan_base, int mem_kind, uint8_t* ground_flag, double* plane, int32_t* best_hyp,
                                 int32_t* best_count, int32_t* hyp_count) {
-  if (!ctx || !scan_off || n_scans < 0) return gr_bad("null pointer or negative count");
-  if (mem_kind != AI_MEM_HOST && mem_kind != AI_MEM_DEVICE) return gr_bad("mem_kind must be AI_MEM_HOST or AI_MEM_DEVICE");
-  if (scan_off[0] != 0) return gr_bad("scan_off must start at 0");
+  const auto bad = [](const char* what) { return bad_arg("ai_ground_planes", what); };
+  if (!ctx || !scan_off || n_scans < 0) return bad("null pointer or negative count");
+  if (mem_kind != AI_MEM_HOST && mem_kind != AI_MEM_DEVICE) return bad("mem_kind must be AI_MEM_HOST or AI_MEM_DEVICE");
+  if (scan_off[0] != 0) return bad("scan_off must start at 0");
   for (int32_t s = 0; s < n_scans; ++s)
-    if (scan_off[s + 1] < scan_off[s]) return gr_bad("scan_off is not monotone");
+    if (scan_off[s + 1] < scan_off[s]) return bad("scan_off is not monotone");
   const int64_t M = scan_off[n_scans];
-  if (M >= ((int64_t)1 << 31) - AI_BLOCK) return gr_bad("M must be below 2^31 - 256");
-  if (!(distance_threshold > 0.0) || !std::isfinite(distance_threshold)) return gr_bad("distance_threshold must be finite and positive");
-  if (n_hyp < 1 || n_hyp > GR_MAX_HYP) return gr_bad("n_hyp must lie in 1 .. 4096");
-  if (scan_base < 0 || scan_base > ((int64_t)1 << 48) - (int64_t)n_scans) return gr_bad("scan_base must be >= 0 and every scan key below 2^48");
-  if ((int64_t)n_scans * n_hyp >= ((int64_t)1 << 31)) return gr_bad("n_scans x n_hyp must be below 2^31");
+  if (M >= ((int64_t)1 << 31) - AI_BLOCK) return bad("M must be below 2^31 - 256");
+  if (!(distance_threshold > 0.0) || !std::isfinite(distance_threshold)) return bad("distance_threshold must be finite and positive");
+  if (n_hyp < 1 || n_hyp > GR_MAX_HYP) return bad("n_hyp must lie in 1 .. 4096");
+  if (scan_base < 0 || scan_base > ((int64_t)1 << 48) - (int64_t)n_scans) return bad("scan_base must be >= 0 and every scan key below 2^48");
+  if ((int64_t)n_scans * n_hyp >= ((int64_t)1 << 31)) return bad("n_scans x n_hyp must be below 2^31");
   const AIKeep keep = ai_keep_rules(moving_index, range_min, range_max);
-  if (M > 0 && keep.use_moving && !label_word) return gr_bad("the moving-object filter needs label_word");
-  if (keep.use_range && !(range_min <= range_max)) return gr_bad("range_min must not exceed range_max (and neither may be NaN)");
-  if (M > 0 && (!scan_xyz || !ground_flag)) return gr_bad("null pointer");
-  if (n_scans > 0 && (!plane || !best_hyp || !best_count)) return gr_bad("null pointer");
+  if (M > 0 && keep.use_moving && !label_word) return bad("the moving-object filter needs label_word");
+  if (keep.use_range && !(range_min <= range_max)) return bad("range_min must not exceed range_max (and neither may be NaN)");
+  if (M > 0 && (!scan_xyz || !ground_flag)) return bad("null pointer");
+  if (n_scans > 0 && (!plane || !best_hyp || !best_count)) return bad("null pointer");
   if (n_scans == 0) return AI_OK;
 
   // the task list of kg_score: scan s owns the slabs slab_off[s] .. slab_off[s + 1] of GR_SLAB consecutive input points each
@@ -268,7 +228,7 @@ extern "C" int ai_ground_planes(ai_ctx* ctx, const float* scan_xyz, const int64_
   std::vector<int64_t> slab_off(n_bound, 0);
   for (int32_t s = 0; s < n_scans; ++s) slab_off[s + 1] = slab_off[s] + (scan_off[s + 1] - scan_off[s] + GR_SLAB - 1) / GR_SLAB;
   const int64_t n_slabs = slab_off[n_scans];
-  if (n_slabs >= ((int64_t)1 << 31) - 1) return gr_bad("too many slabs");   // (out of reach: M / 1024 + n_scans)
+  if (n_slabs >= ((int64_t)1 << 31) - 1) return bad("too many slabs");   // (out of reach: M / 1024 + n_scans)
 
   AI_HIP(hipSetDevice(ctx->device));
   ArenaScope arena_scope(&ctx->arena);
@@ -283,8 +243,8 @@ extern "C" int ai_ground_planes(ai_ctx* ctx, const float* scan_xyz, const int64_
   in.n = M;
   in.keep = keep;
   if (M > 0) {
-    AI_TRY(gr_to_device(scan_xyz, (size_t)M * 3, mem_kind, own_x, &in.xyz, st));
-    if (label_word) AI_TRY(gr_to_device(label_word, (size_t)M, mem_kind, own_w, &in.word, st));
+    AI_TRY(to_device(scan_xyz, (size_t)M * 3, mem_kind, own_x, &in.xyz, st));
+    if (label_word) AI_TRY(to_device(label_word, (size_t)M, mem_kind, own_w, &in.word, st));
   }
   AI_TRY(d_off.alloc(n_bound));
   AI_TRY(d_slab.alloc(n_bound));
@@ -294,15 +254,15 @@ extern "C" int ai_ground_planes(ai_ctx* ctx, const float* scan_xyz, const int64_
   uint8_t* d_flag = nullptr;
   double* d_plane = nullptr;
   int32_t *d_hyp = nullptr, *d_cnt = nullptr, *d_hc = nullptr;
-  AI_TRY(gr_out(ground_flag, (size_t)M, mem_kind, b_flag, &d_flag));
-  AI_TRY(gr_out(plane, (size_t)n_scans * 4, mem_kind, b_plane, &d_plane));
-  AI_TRY(gr_out(best_hyp, (size_t)n_scans, mem_kind, b_hyp, &d_hyp));
-  AI_TRY(gr_out(best_count, (size_t)n_scans, mem_kind, b_cnt, &d_cnt));
-  AI_TRY(gr_out(hyp_count, n_plane, mem_kind, b_hc, &d_hc));
+  AI_TRY(dev_out(ground_flag, (size_t)M, mem_kind, b_flag, &d_flag));
+  AI_TRY(dev_out(plane, (size_t)n_scans * 4, mem_kind, b_plane, &d_plane));
+  AI_TRY(dev_out(best_hyp, (size_t)n_scans, mem_kind, b_hyp, &d_hyp));
+  AI_TRY(dev_out(best_count, (size_t)n_scans, mem_kind, b_cnt, &d_cnt));
+  AI_TRY(dev_out(hyp_count, n_plane, mem_kind, b_hc, &d_hc));
   AI_TRY(hyp_plane.alloc(n_plane * 4));
   AI_TRY(pre.alloc((size_t)M + 1));
   AI_TRY(pos.alloc((size_t)M));
-  const unsigned nb = (unsigned)((M + AI_BLOCK - 1) / AI_BLOCK);
+  const unsigned nb = grid_for(M);
   if (M > 0) {
     AI_TRY(scan_tmp.alloc(ai_scan_tmp_elems(M)));
     hipLaunchKernelGGL(kg_keep, dim3(nb), dim3(AI_BLOCK), 0, st, in, pre.p);
@@ -313,7 +273,7 @@ extern "C" int ai_ground_planes(ai_ctx* ctx, const float* scan_xyz, const int64_
   } else {
     AI_HIP(hipMemsetAsync(pre.p, 0, sizeof(int32_t), st));
   }
-  hipLaunchKernelGGL(kg_hypotheses, dim3((unsigned)((n_plane + AI_BLOCK - 1) / AI_BLOCK)), dim3(AI_BLOCK), 0, st, in,
+  hipLaunchKernelGGL(kg_hypotheses, dim3(grid_for((int64_t)n_plane)), dim3(AI_BLOCK), 0, st, in,
                      (const int64_t*)d_off.p, n_scans, n_hyp, (const int32_t*)pre.p, (const int32_t*)pos.p, seed, (uint64_t)scan_base,
                      hyp_plane.p, d_hc);
   AI_KERNEL_CHECK();

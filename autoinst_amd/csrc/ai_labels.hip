@@ -124,13 +124,6 @@ __global__ __launch_bounds__(AI_BLOCK) void km_inside(const double* __restrict__
   }
 }
 
-// ------------------------------------------------------------------ unique points
-__global__ __launch_bounds__(AI_BLOCK) void ku_compact(const int32_t* __restrict__ pos, int64_t n, int32_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  if (pos[i + 1] != pos[i]) out[pos[i]] = (int32_t)i;
-}
-
 }  // namespace
 
 extern "C" int ai_label_pairs(ai_ctx* ctx, const int32_t* a, const int32_t* b, int64_t n, int mem_kind, int64_t cap, int32_t* pair_a,
@@ -326,7 +319,7 @@ extern "C" int ai_unique_points(ai_ctx* ctx, const double* xyz, int64_t n, int m
   AI_HIP(hipMemcpyAsync(&total, keep.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
   AI_HIP(hipStreamSynchronize(st));
   AI_TRY(out.alloc(total));
-  hipLaunchKernelGGL(ku_compact, dim3(grid_for(n)), dim3(AI_BLOCK), 0, st, (const int32_t*)keep.p, n, out.p);
+  hipLaunchKernelGGL(kq_compact, dim3(grid_for(n)), dim3(AI_BLOCK), 0, st, (const int32_t*)keep.p, n, out.p);
   AI_KERNEL_CHECK();
   if (mem_kind == AI_MEM_DEVICE)
     AI_HIP(hipMemcpyAsync(keep_index, out.p, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToDevice, st));

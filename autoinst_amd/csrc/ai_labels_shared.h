@@ -1,28 +1,14 @@
 // What the label bookkeeping (ai_labels.hip) and the whole-map merge (ai_merge.hip) share: the order-preserving integer forms of a
-// float64, the stable radix-sort / scan wrappers, and the kernels both use unchanged (first-occurrence flags of ai_unique_points;
-// boxes, distinct (value, tag) entries and the common-scalar walk of ai_merge_associate).  Everything has internal linkage.
+// float64 and the kernels both use unchanged (first-occurrence flags of ai_unique_points; boxes, distinct (value, tag) entries and the
+// common-scalar walk of ai_merge_associate).  The host plumbing and the sort / scan wrappers are ai_entry.h's and ai_runs.h's.
+// Everything has internal linkage.
 #pragma once
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "ai_common.h"
+#include "ai_entry.h"
+#include "ai_runs.h"
 
 namespace {
-
-template <typename T>
-int to_device(const T* src, size_t count, int mem_kind, DevBuf<T>& own, const T** dev, hipStream_t st) {
-  if (mem_kind == AI_MEM_DEVICE) {
-    *dev = src;
-    return AI_OK;
-  }
-  AI_TRY(own.alloc(count));
-  AI_HIP(hipMemcpyAsync(own.p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
-  *dev = own.p;
-  return AI_OK;
-}
-
-inline unsigned grid_for(int64_t n) { return (unsigned)((n + AI_BLOCK - 1) / AI_BLOCK); }
 
 // float64 -> uint64 with the same order (and -0.0 == +0.0, as np.unique compares values)
 __device__ __forceinline__ uint64_t ordered_bits(double v) {
@@ -33,13 +19,6 @@ __device__ __forceinline__ uint64_t ordered_bits(double v) {
 __device__ __forceinline__ double from_ordered_bits(uint64_t k) {
   const uint64_t b = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
   return __longlong_as_double((long long)b);
-}
-
-template <typename K>
-__global__ __launch_bounds__(AI_BLOCK) void kl_heads(const K* __restrict__ key, int64_t n, int32_t* __restrict__ head) {
-  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  head[i] = (i == 0 || key[i] != key[i - 1]) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(AI_BLOCK) void km_box_init(unsigned long long* __restrict__ box, int32_t n_inst) {
@@ -115,21 +94,6 @@ __global__ __launch_bounds__(AI_BLOCK) void ku_first_flags(const double* __restr
     for (int a = 0; a < 3; ++a) first |= value_bits(xyz[p * 3 + a]) != value_bits(xyz[q * 3 + a]);
   }
   keep[p] = first ? 1 : 0;  // stable sorts: the first of a run is the smallest original index
-}
-
-template <typename K, typename V>
-int sort_pairs(hipStream_t st, K* kin, K* kout, V* vin, V* vout, int64_t n, int bits) {
-  size_t tmp_bytes = 0;
-  AI_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, kin, kout, vin, vout, (size_t)n, 0, bits, st));
-  DevBuf<uint8_t> tmp;
-  AI_TRY(tmp.alloc(tmp_bytes));
-  AI_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, kin, kout, vin, vout, (size_t)n, 0, bits, st));
-  return AI_OK;
-}
-
-int scan_flags(hipStream_t st, int32_t* flag_to_pos, int64_t n, DevBuf<int32_t>& tmp) {
-  AI_TRY(tmp.alloc(ai_scan_tmp_elems(n)));
-  return ai_exclusive_scan_i32(st, flag_to_pos, flag_to_pos, n, tmp.p);
 }
 
 }  // namespace

@@ -28,16 +28,6 @@ struct MCube {
 // chunks per launch of the centre reduction (MM_RED_BLOCKS * 3 partial sums each)
 #define MM_CENTER_BATCH 4096
 
-// the chunk of position i: the last c with off[c] <= i (chunks without points are passed over)
-__device__ __forceinline__ int32_t chunk_of(const int64_t* __restrict__ off, int32_t n_chunks, int64_t i) {
-  int32_t lo = 0, hi = n_chunks;  // off[lo] <= i < off[hi]
-  while (hi - lo > 1) {
-    const int32_t mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // M1 / M10: the largest local id of every chunk; the first chunk with a non-finite coordinate (bad[0]) or a negative id (bad[1]).
 // A wave whose 64 points lie in one chunk (nearly all do) reduces its ids first and sends one atomic: 2 M points of 72 chunks
 // would otherwise queue at 72 words.
@@ -48,7 +38,7 @@ __global__ __launch_bounds__(AI_BLOCK) void kg_validate(const double* __restrict
   const bool valid = i < m;
   int32_t c = -1, l = 0;
   if (valid) {
-    c = chunk_of(off, n_chunks, i);
+    c = segment_of(off, n_chunks, i);
     const double x = xyz[i * 3], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];
     if (!(isfinite(x) && isfinite(y) && isfinite(z))) atomicMin(&bad[0], c);
     l = inst[i];
@@ -343,13 +333,6 @@ struct ArenaMark {
     a->cur = cur, a->off = off, a->need = need;
   }
 };
-
-template <typename T>
-int to_caller(T* dst, const T* src, size_t count, int mem_kind, hipStream_t st) {
-  if (!dst || count == 0) return AI_OK;
-  AI_HIP(hipMemcpyAsync(dst, src, count * sizeof(T), mem_kind == AI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  return AI_OK;
-}
 
 }  // namespace
 

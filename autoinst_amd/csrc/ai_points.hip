@@ -12,13 +12,9 @@
 // The reference does both with a Python loop over points around an open3d KD-tree query.
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "ai_common.h"
+#include "ai_cells.inc"
 
 namespace {
-
-#include "ai_cells.inc"
 
 // 16 lanes per query point: mean of the float32 feature rows of all source points whose squared
 // distance (sq_dist3) is strictly below radius * radius rounded once -- nanoflann's radius search,
@@ -79,37 +75,8 @@ __global__ __launch_bounds__(AI_BLOCK) void kp_radius_mean(const double* __restr
   if (t == 0 && count) count[i] = cnt;
 }
 
-// The distances from x to the two faces, on one axis, of the box of rings 0..r around cell c: the planes min + (c - r) * cell and
-// min + (c + r + 1) * cell.  A side on which the grid has no cell left counts as infinitely far.  Every step is rounded on its own
-// (no contraction), so that the slack of kp_nn1's stop rule can be counted and tests/points_cases.py can restate it.
-__device__ __forceinline__ double face_gap(double x, double mn, double cell, int c, int r, int n) {
-#pragma clang fp contract(off)
-  const double lo = (c - r - 1 >= 0) ? x - (mn + (double)(c - r) * cell) : INFINITY;
-  const double hi = (c + r + 1 <= n - 1) ? (mn + (double)(c + r + 1) * cell) - x : INFINITY;
-  return fmin(lo, hi);
-}
-
-// |min| + (n + 1) * cell + |x|: above every magnitude that enters an index or a face on this axis
-__device__ __forceinline__ double axis_mag(double x, double mn, double cell, int n) {
-#pragma clang fp contract(off)
-  return (fabs(mn) + (double)(n + 1) * cell) + fabs(x);
-}
-
 // One thread per fine point: exact nearest source point (smallest sq_dist3, ties to the smaller source index; distance = its
-// correctly rounded sqrt) by growing rings of cells.
-// Stop rule (kn_nearest's, ai_prep.hip): a source outside rings 0..r has, on some axis, a stored cell index k >= c + r + 1 (or
-// <= c - r - 1), so it lies beyond that face F = min + k * cell of the box of those rings -- up to the rounding of pcell_of.  With
-// u = 2^-53: the index is floor(fl(fl(p - min) * inv_cell)) and inv_cell = fl(1 / cell), three roundings, so fl(..) >= k only
-// gives p - min >= k * cell * (1 - 4u) (and < k * cell * (1 + 4u) on the low side; the clamp to n - 1 only lowers a stored index):
-// the source may lie 4u * k * cell inside the face.  face_gap computes |F - x| with three more roundings, of k * cell, of F and
-// of the difference: at most u * (k * cell + |F| + |F| + |x|) off.  With mag >= |min| + (n + 1) * cell + |x| on every axis, which
-// bounds k * cell, |F| and |x|, all of it stays below 8u * mag; `slack` is 16u * mag = 8 ulps of mag, as in kn_nearest.  So every
-// unvisited source is more than lb = (nearest face gap) - slack away, in exact arithmetic.  sq_dist3 rounds five times, hence
-// returns at least d^2 * (1 - 5u) for a source at distance d > lb; sqrt(best) * (1 + 8u) <= lb gives best <= lb^2 * (1 - 11u)
-// after the rounding of the sqrt and of the product: strictly below the square of every unvisited source, so none is nearer or
-// tied.  The face gap is at least r * cell, the bound the rule had before the rounding was counted (a source that fl(p - min)
-// had rounded up onto a cell border was missed when best == r * cell): an extra ring is searched only when sqrt(best) is within
-// the slack of it.  With no cell left on any side lb is +inf and the loop ends.
+// correctly rounded sqrt) by growing rings of cells.  Stop rule: the ring searches' (ai_cells.inc, where it is derived), for the best.
 __global__ __launch_bounds__(AI_BLOCK) void kp_nn1(const double* __restrict__ q, int64_t nq, PGrid g, double cell,
                                                    const double* __restrict__ X, const double* __restrict__ Y,
                                                    const double* __restrict__ Z, const int32_t* __restrict__ order,
@@ -194,7 +161,7 @@ extern "C" int ai_radius_mean_pool(ai_ctx* ctx, const double* query_xyz, int64_t
     o = d_out.p;
     c = d_cnt.p;
   }
-  const unsigned gq = (unsigned)((nq * 16 + AI_BLOCK - 1) / AI_BLOCK);
+  const unsigned gq = grid_for(nq * 16);
   hipLaunchKernelGGL(kp_radius_mean, dim3(gq), dim3(AI_BLOCK), 0, st, dq, nq, C.g, radius, (const double*)C.X.p, (const double*)C.Y.p,
                      (const double*)C.Z.p, (const int32_t*)C.order.p, (const int32_t*)C.cstart.p, (const int32_t*)C.cend.p, df, dim, o, c);
   AI_KERNEL_CHECK();
@@ -231,7 +198,7 @@ extern "C" int ai_nn1_project(ai_ctx* ctx, const double* to_xyz, int64_t nt, con
     oi = d_idx.p;
     od = d_dist.p;
   }
-  const unsigned gq = (unsigned)((nt + AI_BLOCK - 1) / AI_BLOCK);
+  const unsigned gq = grid_for(nt);
   hipLaunchKernelGGL(kp_nn1, dim3(gq), dim3(AI_BLOCK), 0, st, dt, nt, C.g, C.cell, (const double*)C.X.p, (const double*)C.Y.p,
                      (const double*)C.Z.p, (const int32_t*)C.order.p, (const int32_t*)C.cstart.p, (const int32_t*)C.cend.p, oi, od);
   AI_KERNEL_CHECK();

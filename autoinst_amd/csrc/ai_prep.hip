@@ -33,26 +33,11 @@
 #include <climits>
 #include <cmath>
 
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "ai_common.h"
+#include "ai_cells.inc"
 
 namespace {
-
-unsigned grid_for(int64_t n) { return (unsigned)((n + AI_BLOCK - 1) / AI_BLOCK); }
-
-template <typename T>
-int to_device(const T* src, size_t count, int mem_kind, DevBuf<T>& own, const T** dev, hipStream_t st) {
-  if (mem_kind == AI_MEM_DEVICE) {
-    *dev = src;
-    return AI_OK;
-  }
-  AI_TRY(own.alloc(count));
-  AI_HIP(hipMemcpyAsync(own.p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
-  *dev = own.p;
-  return AI_OK;
-}
 
 // ----------------------------------------------------------------------------- bounds
 
@@ -120,21 +105,6 @@ int bounds(ai_ctx* ctx, const double* d_xyz, int64_t n, double mn[3], double mx[
   return AI_OK;
 }
 
-template <typename K, typename V>
-int sort_pairs(hipStream_t st, K* key, K* skey, V* val, V* sval, int64_t n, int bits) {
-  size_t tmp_bytes = 0;
-  AI_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key, skey, val, sval, (size_t)n, 0, bits, st));
-  DevBuf<uint8_t> tmp;
-  AI_TRY(tmp.alloc(tmp_bytes));
-  AI_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, key, skey, val, sval, (size_t)n, 0, bits, st));
-  return AI_OK;
-}
-
-__global__ __launch_bounds__(AI_BLOCK) void kq_compact(const int32_t* __restrict__ pos, int64_t n, int32_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  if (i < n && pos[i + 1] != pos[i]) out[pos[i]] = (int32_t)i;
-}
-
 // ----------------------------------------------------------------------------- box select
 
 // cnt[b * ntile + t] = #points of tile t (AI_BLOCK points) strictly inside box b (lo = box[6b..6b+2], hi = box[6b+3..6b+5])
@@ -195,17 +165,6 @@ __global__ void kb_box_offsets(const int64_t* __restrict__ off, int32_t nbox, in
 
 // ----------------------------------------------------------------------------- statistical inliers
 
-struct KGrid {
-  double minx, miny, minz, inv_cell, cell;
-  int nx, ny, nz;
-};
-
-__device__ __forceinline__ void kcell_of(const KGrid& g, double x, double y, double z, int& cx, int& cy, int& cz) {
-  cx = min(max((int)floor((x - g.minx) * g.inv_cell), 0), g.nx - 1);
-  cy = min(max((int)floor((y - g.miny) * g.inv_cell), 0), g.ny - 1);
-  cz = min(max((int)floor((z - g.minz) * g.inv_cell), 0), g.nz - 1);
-}
-
 // sort key: row (z, y) in the high bits, x cell in the low 32
 __global__ __launch_bounds__(AI_BLOCK) void kq_keys(const double* __restrict__ xyz, int64_t n, KGrid g, uint64_t* __restrict__ key,
                                                     int32_t* __restrict__ idx) {
@@ -217,69 +176,11 @@ __global__ __launch_bounds__(AI_BLOCK) void kq_keys(const double* __restrict__ x
   idx[i] = (int32_t)i;
 }
 
-__global__ __launch_bounds__(AI_BLOCK) void kq_gather(const double* __restrict__ xyz, const int32_t* __restrict__ order,
-                                                      const uint64_t* __restrict__ skey, int64_t n, double* __restrict__ X,
-                                                      double* __restrict__ Y, double* __restrict__ Z, int32_t* __restrict__ scx,
-                                                      int32_t* __restrict__ rstart, int32_t* __restrict__ rend) {
-  const int64_t p = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  if (p >= n) return;
-  const int64_t o = order[p];
-  X[p] = xyz[o * 3];
-  Y[p] = xyz[o * 3 + 1];
-  Z[p] = xyz[o * 3 + 2];
-  const uint64_t k = skey[p];
-  scx[p] = (int32_t)(uint32_t)k;
-  const uint32_t row = (uint32_t)(k >> 32);
-  if (p == 0 || (uint32_t)(skey[p - 1] >> 32) != row) rstart[row] = (int32_t)p;
-  if (p == n - 1 || (uint32_t)(skey[p + 1] >> 32) != row) rend[row] = (int32_t)(p + 1);
-}
-
-// (dx*dx + dy*dy) + dz*dz with every step rounded, as the brute-force restatement and cKDTree's distances: without the
-// pragma the default -ffp-contract=fast fuses the adds into v_fmac_f64
-__device__ __forceinline__ double sq_dist3(double x, double y, double z, double px, double py, double pz) {
-#pragma clang fp contract(off)
-  const double dx = x - px, dy = y - py, dz = z - pz;
-  return (dx * dx + dy * dy) + dz * dz;
-}
-
-// keep the K smallest values seen in best[0..K-1] (ascending); compile-time indices only, so the list stays in registers
-template <int K>
-__device__ __forceinline__ void knn_insert(double (&best)[K], double d2) {
-  if (d2 < best[K - 1]) {
-#pragma unroll
-    for (int j = K - 1; j > 0; --j) best[j] = d2 < best[j - 1] ? best[j - 1] : fmin(d2, best[j]);
-    best[0] = fmin(best[0], d2);
-  }
-}
-
-// kp_nn1's two helpers (ai_points.hip, where the stop rule is derived), every step rounded on its own: the distance from x to the
-// nearer face, on one axis, of the box of rings 0..r around cell c (a side without a cell left is infinitely far), and a
-// magnitude above everything that enters an index or a face on that axis.
-__device__ __forceinline__ double face_gap(double x, double mn, double cell, int c, int r, int n) {
-#pragma clang fp contract(off)
-  const double lo = (c - r - 1 >= 0) ? x - (mn + (double)(c - r) * cell) : INFINITY;
-  const double hi = (c + r + 1 <= n - 1) ? (mn + (double)(c + r + 1) * cell) - x : INFINITY;
-  return fmin(lo, hi);
-}
-
-__device__ __forceinline__ double axis_mag(double x, double mn, double cell, int n) {
-#pragma clang fp contract(off)
-  return (fabs(mn) + (double)(n + 1) * cell) + fabs(x);
-}
-
 // One thread per point (in cell order, so that a wave's queries are neighbours): the k <= K smallest squared distances to the
 // cloud (the point itself included) by rings of cells around its own cell.  Ring r is the shell of Chebyshev cell distance r: in
 // the rows (dz, dy) on the shell's faces the whole x range [cx - r, cx + r], in the other rows the cells cx - r and cx + r.
-// Stop rule: kp_nn1's (ai_points.hip), for the k-th best in place of the best.  kcell_of has pcell_of's three roundings (the
-// subtraction, the product, inv_cell = fl(1 / cell)), so a point outside rings 0..r, whose stored cell index is beyond c - r ..
-// c + r on some axis, may lie at most 4u * k * cell inside that face of the box of those rings (u = 2^-53); face_gap adds three
-// roundings of its own.  All of it stays below 8u * mag, and `slack` is 16u * mag = 8 ulps of mag: every unvisited point is more
-// than lb = (nearest face gap) - slack away in exact arithmetic, so its sq_dist3 (five roundings) is at least lb^2 * (1 - 5u).
-// sqrt(kth) * (1 + 8u) <= lb gives kth <= lb^2 * (1 - 11u): strictly below the square of every unvisited point.  The k smallest
-// squares seen are then the k smallest of the whole cloud, whatever the grid is.  (sqrt(kth) <= r * cell, the rule before the
-// rounding was counted, missed a point that fl(p - min) had rounded up onto a cell border when sqrt(kth) was within a few ulps
-// of r * cell: tests/prep_cases.py finds such clouds.)  The face gap is r * cell for a query on a face of its own cell and more
-// elsewhere; with no cell left on any side lb is +inf and the loop ends.
+// Stop rule: the ring searches' (ai_cells.inc, where it is derived), for the k-th best in place of the best: the k smallest squares
+// seen are then the k smallest of the whole cloud, whatever the grid is.
 // avg[order[p]] = (sum of the k distances in ascending order) / k.
 template <int K>
 __global__ __launch_bounds__(AI_BLOCK) void kq_knn_avg(int64_t n, int32_t k, KGrid g, const double* __restrict__ X,
@@ -410,18 +311,6 @@ __global__ __launch_bounds__(AI_BLOCK) void kv_keys(const double* __restrict__ x
   const uint64_t iz = (uint64_t)(int64_t)floor((xyz[i * 3 + 2] - g.vminz) / g.size);
   key[i] = (ix << g.sy) | (iy << g.sz) | iz;
   idx[i] = (int32_t)i;
-}
-
-__global__ __launch_bounds__(AI_BLOCK) void kv_heads(const uint64_t* __restrict__ skey, int64_t n, int32_t* __restrict__ head) {
-  const int64_t p = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  if (p < n) head[p] = (p == 0 || skey[p] != skey[p - 1]) ? 1 : 0;
-}
-
-// vid = exclusive scan of the heads: start[vid[p]] = p at every head, start[m] = n
-__global__ __launch_bounds__(AI_BLOCK) void kv_starts(const int32_t* __restrict__ vid, int64_t n, int32_t* __restrict__ start) {
-  const int64_t p = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  if (p < n && (p == 0 || vid[p + 1] != vid[p])) start[vid[p]] = (int32_t)p;
-  if (p == n) start[vid[n]] = (int32_t)n;
 }
 
 // one thread per voxel: the sum of its points in input-index order (the sort is stable), divided by their count
@@ -557,12 +446,6 @@ __global__ __launch_bounds__(AI_BLOCK) void kn_nearest(int64_t m, NGrid g, const
   }
   nn_idx[v] = bi;
   if (nn_dist) nn_dist[v] = sqrt(best);
-}
-
-int bits_for(int64_t count) {  // bits that hold 0 .. count - 1
-  int b = 0;
-  while (b < 63 && ((int64_t)1 << b) < count) ++b;
-  return b;
 }
 
 }  // namespace
@@ -802,7 +685,7 @@ extern "C" int ai_voxel_down_sample(ai_ctx* ctx, const double* xyz, int64_t n, d
   hipLaunchKernelGGL(kv_keys, dim3(gb), dim3(AI_BLOCK), 0, st, dx, n, g, key.p, idx.p);
   AI_KERNEL_CHECK();
   AI_TRY(sort_pairs(st, key.p, skey.p, idx.p, order.p, n, std::max(1, bits[0] + bits[1] + bits[2])));
-  hipLaunchKernelGGL(kv_heads, dim3(gb), dim3(AI_BLOCK), 0, st, (const uint64_t*)skey.p, n, vid.p);
+  hipLaunchKernelGGL(kl_heads<uint64_t>, dim3(gb), dim3(AI_BLOCK), 0, st, (const uint64_t*)skey.p, n, vid.p);
   AI_KERNEL_CHECK();
   AI_TRY(ai_exclusive_scan_i32(st, vid.p, vid.p, n, scan_tmp.p));
   hipLaunchKernelGGL(kv_starts, dim3(grid_for(n + 1)), dim3(AI_BLOCK), 0, st, (const int32_t*)vid.p, n, start.p);
@@ -888,7 +771,7 @@ extern "C" int ai_voxel_down_sample_nearest(ai_ctx* ctx, const double* xyz, int6
   hipLaunchKernelGGL(kv_keys, dim3(gb), dim3(AI_BLOCK), 0, st, dx, n, g, key.p, idx.p);
   AI_KERNEL_CHECK();
   AI_TRY(sort_pairs(st, key.p, skey.p, idx.p, order.p, n, std::max(1, bits[0] + bits[1] + bits[2])));
-  hipLaunchKernelGGL(kv_heads, dim3(gb), dim3(AI_BLOCK), 0, st, (const uint64_t*)skey.p, n, vid.p);
+  hipLaunchKernelGGL(kl_heads<uint64_t>, dim3(gb), dim3(AI_BLOCK), 0, st, (const uint64_t*)skey.p, n, vid.p);
   AI_KERNEL_CHECK();
   AI_TRY(ai_exclusive_scan_i32(st, vid.p, vid.p, n, scan_tmp.p));
   hipLaunchKernelGGL(kv_starts, dim3(grid_for(n + 1)), dim3(AI_BLOCK), 0, st, (const int32_t*)vid.p, n, start.p);

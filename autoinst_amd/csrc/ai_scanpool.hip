@@ -7,7 +7,7 @@
 //   (scan)     exclusive scan of the flags: the survivors keep their order in scan_xyz;
 //   ks_keys    the survivors' 64-bit cell keys ix << sy | iy << sz | iz and their source indices;
 //   (sort)     stable rocPRIM radix sort by key: ascending (ix, iy, iz), then ascending position in scan_xyz (R4);
-//   kv-style heads / scan / starts: the table of occupied cells (sorted distinct keys with their runs); no dense grid;
+//   kl_heads / scan / kv_starts (ai_runs.h): the table of occupied cells (sorted distinct keys with their runs); no dense grid;
 //   ks_gather  coordinates and scan positions in sort order, the distinct keys;
 //   ks_pool    16 lanes per query: 9 binary searches (one (ix, iy) row of three iz cells is one key range), shared membership
 //              tests (lane t tests candidate t), then the group walks the ballot in candidate order and every lane adds its
@@ -19,14 +19,10 @@
 #include <climits>
 #include <cmath>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "ai_common.h"
+#include "ai_cells.inc"
 #include "ai_xform.h"  // ai_xf: the fixed-order transform (R1)
 
 namespace {
-
-#include "ai_cells.inc"
 
 #define SP_TILE 256           // chunk records per LDS tile of ks_flag
 #define SP_MAX_INDEX 1073741824.0  // |cell index| < 2^30
@@ -43,27 +39,6 @@ struct SPGrid {
   int32_t sy, sz;      // key = ix << sy | iy << sz | iz
 };
 
-unsigned sp_grid_for(int64_t n) { return (unsigned)((n + AI_BLOCK - 1) / AI_BLOCK); }
-
-int sp_bits_for(int64_t count) {  // bits that hold 0 .. count - 1
-  int b = 0;
-  while (b < 63 && ((int64_t)1 << b) < count) ++b;
-  return b;
-}
-
-// the last s with off[s] <= i (scans without points are skipped: their successor starts at the same offset)
-__device__ __forceinline__ int32_t sp_segment_of(const int64_t* __restrict__ off, int32_t n, int64_t i) {
-  int32_t a = 0, b = n;  // the answer is in [a, b)
-  while (b - a > 1) {
-    const int32_t h = (a + b) >> 1;
-    if (off[h] <= i)
-      a = h;
-    else
-      b = h;
-  }
-  return a;
-}
-
 __device__ __forceinline__ bool sp_in_box(const SPChunk& c, double x, double y, double z) {
   return x > c.lo[0] && y > c.lo[1] && z > c.lo[2] && x < c.hi[0] && y < c.hi[1] && z < c.hi[2];
 }
@@ -71,7 +46,7 @@ __device__ __forceinline__ bool sp_in_box(const SPChunk& c, double x, double y, 
 // the transformed point of source index i and its scan position
 __device__ __forceinline__ int32_t sp_source(const double* __restrict__ xyz, const int64_t* __restrict__ scan_off, int32_t n_scans,
                                              const double* __restrict__ T, int64_t i, double& x, double& y, double& z) {
-  const int32_t s = sp_segment_of(scan_off, n_scans, i);
+  const int32_t s = segment_of(scan_off, n_scans, i);
   ai_xf(T + (int64_t)s * 16, xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2], x, y, z);
   return s;
 }
@@ -130,18 +105,6 @@ __global__ __launch_bounds__(AI_BLOCK) void ks_keys(const double* __restrict__ x
   idx[p] = (int32_t)i;
 }
 
-__global__ __launch_bounds__(AI_BLOCK) void ks_heads(const uint64_t* __restrict__ skey, int64_t n, int32_t* __restrict__ head) {
-  const int64_t p = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  if (p < n) head[p] = (p == 0 || skey[p] != skey[p - 1]) ? 1 : 0;
-}
-
-// vid = exclusive scan of the heads: start[vid[p]] = p at every head, start[m] = n
-__global__ __launch_bounds__(AI_BLOCK) void ks_starts(const int32_t* __restrict__ vid, int64_t n, int32_t* __restrict__ start) {
-  const int64_t p = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  if (p < n && (p == 0 || vid[p + 1] != vid[p])) start[vid[p]] = (int32_t)p;
-  if (p == n) start[vid[n]] = (int32_t)n;
-}
-
 // the survivors in sort order: transformed coordinates, scan position; ukey[v] = the key of occupied cell v (ascending)
 __global__ __launch_bounds__(AI_BLOCK) void ks_gather(const double* __restrict__ xyz, const int64_t* __restrict__ scan_off,
                                                       int32_t n_scans, const double* __restrict__ T, const int32_t* __restrict__ order,
@@ -176,7 +139,7 @@ __global__ __launch_bounds__(AI_BLOCK) void ks_pool(const double* __restrict__ q
   if (i >= nq) return;
   const int shift = (int)(threadIdx.x & 48);  // where the group's 16 bits sit in the wave's ballot
   const double x = q[i * 3], y = q[i * 3 + 1], z = q[i * 3 + 2];
-  const SPChunk ck = chunks[sp_segment_of(query_off, n_chunks, i)];
+  const SPChunk ck = chunks[segment_of(query_off, n_chunks, i)];
   const double fx = floor(x * g.inv_cell), fy = floor(y * g.inv_cell), fz = floor(z * g.inv_cell);
   double acc[MAXK];
 #pragma unroll
@@ -241,35 +204,31 @@ __global__ __launch_bounds__(AI_BLOCK) void ks_pool(const double* __restrict__ q
   if (t == 0 && count) count[i] = cnt;
 }
 
-int sp_bad(const char* what) {
-  ai_set_error("ai_scan_pool: %s", what);
-  return AI_ERR_BAD_ARG;
-}
-
 }  // namespace
 
 extern "C" int ai_scan_pool(ai_ctx* ctx, const double* scan_xyz, const int64_t* scan_off, int32_t n_scans, const double* T_scan2pcd,
                             const float* scan_feat, int32_t dim, const double* query_xyz, const int64_t* query_off, int32_t n_chunks,
                             const double* boxes, const int32_t* scan_win, double radius, int mem_kind, double* out, int32_t* count_out) {
-  if (!ctx || !scan_off || !query_off || n_scans < 0 || n_chunks < 0) return sp_bad("null pointer or negative count");
-  if (dim < 1 || dim > 384) return sp_bad("dim must be 1 .. 384");
-  if (!(radius > 0.0) || !std::isfinite(radius)) return sp_bad("radius must be positive and finite");
-  if (scan_off[0] != 0 || query_off[0] != 0) return sp_bad("an offset array must start at 0");
+  const auto bad = [](const char* what) { return bad_arg("ai_scan_pool", what); };
+  if (!ctx || !scan_off || !query_off || n_scans < 0 || n_chunks < 0) return bad("null pointer or negative count");
+  if (dim < 1 || dim > 384) return bad("dim must be 1 .. 384");
+  if (!(radius > 0.0) || !std::isfinite(radius)) return bad("radius must be positive and finite");
+  if (scan_off[0] != 0 || query_off[0] != 0) return bad("an offset array must start at 0");
   for (int32_t s = 0; s < n_scans; ++s)
-    if (scan_off[s + 1] < scan_off[s]) return sp_bad("scan_off is not monotone");
+    if (scan_off[s + 1] < scan_off[s]) return bad("scan_off is not monotone");
   for (int32_t c = 0; c < n_chunks; ++c)
-    if (query_off[c + 1] < query_off[c]) return sp_bad("query_off is not monotone");
+    if (query_off[c + 1] < query_off[c]) return bad("query_off is not monotone");
   const int64_t M = scan_off[n_scans], Nq = query_off[n_chunks];
   const int64_t lim = ((int64_t)1 << 31) - AI_BLOCK;
-  if (M >= lim || Nq >= lim) return sp_bad("M and Nq must be below 2^31 - 256");
+  if (M >= lim || Nq >= lim) return bad("M and Nq must be below 2^31 - 256");
   if ((n_scans > 0 && !T_scan2pcd) || (n_chunks > 0 && (!boxes || !scan_win)) || (M > 0 && (!scan_xyz || !scan_feat)) ||
       (Nq > 0 && (!query_xyz || !out)))
-    return sp_bad("null pointer");
+    return bad("null pointer");
   for (int32_t s = 0; s < n_scans; ++s) {
     const double* T = T_scan2pcd + (size_t)s * 16;
     for (int k = 0; k < 12; ++k)
-      if (!std::isfinite(T[k])) return sp_bad("T_scan2pcd is not finite");
-    if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return sp_bad("the last row of T_scan2pcd must be (0, 0, 0, 1)");
+      if (!std::isfinite(T[k])) return bad("T_scan2pcd is not finite");
+    if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return bad("the last row of T_scan2pcd must be (0, 0, 0, 1)");
   }
   const double cell = radius * (1.0 + 1e-9), inv_cell = 1.0 / cell;
   std::vector<SPChunk> hc((size_t)std::max(n_chunks, 1));
@@ -279,13 +238,13 @@ extern "C" int ai_scan_pool(ai_ctx* ctx, const double* scan_xyz, const int64_t* 
     for (int a = 0; a < 3; ++a) {
       k.lo[a] = boxes[(size_t)c * 6 + a];
       k.hi[a] = boxes[(size_t)c * 6 + 3 + a];
-      if (!std::isfinite(k.lo[a]) || !std::isfinite(k.hi[a])) return sp_bad("a box bound is not finite");
+      if (!std::isfinite(k.lo[a]) || !std::isfinite(k.hi[a])) return bad("a box bound is not finite");
       lo[a] = std::min(lo[a], k.lo[a]);
       hi[a] = std::max(hi[a], k.hi[a]);
     }
     k.w0 = scan_win[(size_t)c * 2];
     k.w1 = scan_win[(size_t)c * 2 + 1];
-    if (k.w0 < 0 || k.w1 > n_scans || k.w0 > k.w1) return sp_bad("scan_win must satisfy 0 <= first <= last <= n_scans");
+    if (k.w0 < 0 || k.w1 > n_scans || k.w0 > k.w1) return bad("scan_win must satisfy 0 <= first <= last <= n_scans");
   }
   if (M == 0 && Nq == 0) return AI_OK;  // nothing to examine and nothing to write
   // the key fields: every survivor is strictly inside a box, so its index lies in floor(lo * inv) .. floor(hi * inv) per axis.
@@ -296,12 +255,12 @@ extern "C" int ai_scan_pool(ai_ctx* ctx, const double* scan_xyz, const int64_t* 
   int32_t bias[3] = {0, 0, 0};
   for (int a = 0; a < 3 && Nq > 0; ++a) {
     const double i0 = floor(lo[a] * inv_cell), i1 = floor(hi[a] * inv_cell);
-    if (!(fabs(i0) < SP_MAX_INDEX) || !(fabs(i1) < SP_MAX_INDEX)) return sp_bad("a cell index does not fit its key field (|index| >= 2^30)");
+    if (!(fabs(i0) < SP_MAX_INDEX) || !(fabs(i1) < SP_MAX_INDEX)) return bad("a cell index does not fit its key field (|index| >= 2^30)");
     bias[a] = (int32_t)i0;
-    bits[a] = sp_bits_for(std::max((int64_t)i1 - (int64_t)i0 + 1, (int64_t)1));
-    if (bits[a] > 30) return sp_bad("a cell index does not fit its key field (the boxes span 2^30 cells or more on an axis)");
+    bits[a] = bits_for(std::max((int64_t)i1 - (int64_t)i0 + 1, (int64_t)1));
+    if (bits[a] > 30) return bad("a cell index does not fit its key field (the boxes span 2^30 cells or more on an axis)");
   }
-  if (bits[0] + bits[1] + bits[2] > 63) return sp_bad("the cell indices of the boxes do not fit a 64-bit key");
+  if (bits[0] + bits[1] + bits[2] > 63) return bad("the cell indices of the boxes do not fit a 64-bit key");
   g.bx = bias[0];
   g.by = bias[1];
   g.bz = bias[2];
@@ -342,14 +301,14 @@ extern "C" int ai_scan_pool(ai_ctx* ctx, const double* scan_xyz, const int64_t* 
   if (M > 0) {
     AI_TRY(pos.alloc((size_t)M + 1));
     AI_TRY(scan_tmp.alloc(ai_scan_tmp_elems(M)));
-    hipLaunchKernelGGL(ks_flag, dim3(sp_grid_for(M)), dim3(AI_BLOCK), 0, st, ds, M, (const int64_t*)d_soff.p, n_scans, (const double*)d_T.p,
+    hipLaunchKernelGGL(ks_flag, dim3(grid_for(M)), dim3(AI_BLOCK), 0, st, ds, M, (const int64_t*)d_soff.p, n_scans, (const double*)d_T.p,
                        (const SPChunk*)d_chunks.p, n_chunks, pos.p, d_err.p);
     AI_KERNEL_CHECK();
     AI_TRY(ai_exclusive_scan_i32(st, pos.p, pos.p, M, scan_tmp.p));
     AI_HIP(hipMemcpyAsync(&ns, pos.p + M, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     AI_HIP(hipMemcpyAsync(&herr, d_err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     AI_HIP(hipStreamSynchronize(st));
-    if (herr) return sp_bad("a scan coordinate is not finite");
+    if (herr) return bad("a scan coordinate is not finite");
   }
   if (Nq == 0) return AI_OK;  // no chunk has a query: the arguments are checked, there is nothing to write
   AI_TRY(key.alloc(ns));
@@ -366,20 +325,17 @@ extern "C" int ai_scan_pool(ai_ctx* ctx, const double* scan_xyz, const int64_t* 
   if (ns > 0) {
     DevBuf<int32_t> scan_tmp2;
     DevBuf<uint8_t> tmp;
-    const unsigned gb = sp_grid_for(ns);
-    hipLaunchKernelGGL(ks_keys, dim3(sp_grid_for(M)), dim3(AI_BLOCK), 0, st, ds, M, (const int64_t*)d_soff.p, n_scans, (const double*)d_T.p,
+    const unsigned gb = grid_for(ns);
+    hipLaunchKernelGGL(ks_keys, dim3(grid_for(M)), dim3(AI_BLOCK), 0, st, ds, M, (const int64_t*)d_soff.p, n_scans, (const double*)d_T.p,
                        (const int32_t*)pos.p, g, key.p, idx.p);
     AI_KERNEL_CHECK();
     const int kbits = std::max(1, bits[0] + bits[1] + bits[2]);
-    size_t tmp_bytes = 0;
-    AI_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key.p, skey.p, idx.p, order.p, (size_t)ns, 0, kbits, st));
-    AI_TRY(tmp.alloc(tmp_bytes));
-    AI_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, key.p, skey.p, idx.p, order.p, (size_t)ns, 0, kbits, st));
+    AI_TRY(sort_pairs(st, key.p, skey.p, idx.p, order.p, (int64_t)ns, kbits, tmp));
     AI_TRY(scan_tmp2.alloc(ai_scan_tmp_elems(ns)));
-    hipLaunchKernelGGL(ks_heads, dim3(gb), dim3(AI_BLOCK), 0, st, (const uint64_t*)skey.p, (int64_t)ns, vid.p);
+    hipLaunchKernelGGL(kl_heads<uint64_t>, dim3(gb), dim3(AI_BLOCK), 0, st, (const uint64_t*)skey.p, (int64_t)ns, vid.p);
     AI_KERNEL_CHECK();
     AI_TRY(ai_exclusive_scan_i32(st, vid.p, vid.p, ns, scan_tmp2.p));
-    hipLaunchKernelGGL(ks_starts, dim3(sp_grid_for((int64_t)ns + 1)), dim3(AI_BLOCK), 0, st, (const int32_t*)vid.p, (int64_t)ns, start.p);
+    hipLaunchKernelGGL(kv_starts, dim3(grid_for((int64_t)ns + 1)), dim3(AI_BLOCK), 0, st, (const int32_t*)vid.p, (int64_t)ns, start.p);
     AI_KERNEL_CHECK();
     AI_HIP(hipMemcpyAsync(&m, vid.p + ns, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     hipLaunchKernelGGL(ks_gather, dim3(gb), dim3(AI_BLOCK), 0, st, ds, (const int64_t*)d_soff.p, n_scans, (const double*)d_T.p,
@@ -397,7 +353,7 @@ extern "C" int ai_scan_pool(ai_ctx* ctx, const double* scan_xyz, const int64_t* 
       c = d_cnt.p;
     }
   }
-  const unsigned gq = (unsigned)((Nq * 16 + AI_BLOCK - 1) / AI_BLOCK);
+  const unsigned gq = grid_for(Nq * 16);
   if (dim <= 96)
     hipLaunchKernelGGL(ks_pool<6>, dim3(gq), dim3(AI_BLOCK), 0, st, dq, Nq, (const int64_t*)d_qoff.p, n_chunks, (const SPChunk*)d_chunks.p,
                        g, radius, (int64_t)m, (const uint64_t*)ukey, (const int32_t*)start.p, (const double*)X.p, (const double*)Y.p,
@@ -413,6 +369,6 @@ extern "C" int ai_scan_pool(ai_ctx* ctx, const double* scan_xyz, const int64_t* 
     if (count_out) AI_HIP(hipMemcpyAsync(count_out, c, (size_t)Nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   }
   AI_HIP(hipStreamSynchronize(st));
-  if (herr) return sp_bad("a query coordinate is not finite, or its cell index does not fit (|index| >= 2^30)");
+  if (herr) return bad("a query coordinate is not finite, or its cell index does not fit (|index| >= 2^30)");
   return AI_OK;
 }

@@ -3,6 +3,7 @@ all of them, the stop rule `kq_knn_avg` had before the rounding of `kcell_of` wa
 case while the shipped one misses none (also in a seeded search), a list of deliberately wrong rules is each rejected by a
 fixture built for it, and no fixture but the ones built to sit on the threshold lies inside the statistics bound.  No GPU, no
 library."""
+import os
 import re
 
 import numpy as np
@@ -24,18 +25,31 @@ def _models(c):
 
 # ------------------------------------------------------------------------------------------------- constants
 def test_the_three_ring_searches_share_one_stop_rule():
-    """`kq_knn_avg`, `kf_knn_avg` (ai_finish.hip) and `kp_nn1` (ai_points.hip) use the same slack, the same ulps in the comparison
-    and, character for character, the same two helpers."""
-    prep, fin, pts = (pc._read(pc._CSRC, f) for f in ("ai_prep.hip", "ai_finish.hip", "ai_points.hip"))
-    want = (pc.K["SLACK_ULPS"], pc.K["STOP_ULPS"])
-    assert pc.stop_constants(pts, "cell", "best", "kp_nn1") == want
-    assert pc.stop_constants(fin, r"g\.cell", "kth", "kf_knn_avg") == want
+    """`kq_knn_avg` (ai_prep.hip), `kf_knn_avg`, `kf_nn1` (ai_finish.hip) and `kp_nn1` (ai_points.hip) use the same slack and the same
+    ulps in the comparison, and all four call the one `face_gap` and the one `axis_mag` that exist under csrc (ai_cells.inc).
+
+    The two kNN search bodies, and the two 1-NN search bodies, are still compared as text: written once as `__forceinline__`
+    functions they gave the parent's instructions (up to exchanged operands of commutative ones) in `kq_knn_avg` alone; in
+    `kf_knn_avg<20 / 32 / 64>` the same 1301 / 1822 / 3430 instructions came out in another order, and `kp_nn1` / `kf_nn1` came out
+    with 496 / 507 instructions for 502 / 513 (tools/asm_identity.py), so the bodies stay in their kernels."""
+    sources = {f: pc._read(pc._CSRC, f) for f in sorted(os.listdir(pc._CSRC)) if f.endswith((".hip", ".h", ".inc"))}
     for helper in ("face_gap", "axis_mag"):
-        bodies = [re.search(r"double %s\([^)]*\) \{.*?\n\}" % helper, text, re.S).group(0) for text in (prep, fin, pts)]
-        assert bodies[0] == bodies[1] == bodies[2], helper
-    knn = [re.search(r"void k[qf]_knn_avg\(.*?\n\}", text, re.S).group(0) for text in (prep, fin)]
-    loops = [body[body.index("  double best[K];"):] for body in knn]
+        defined = [f for f, text in sources.items() for _ in re.finditer(r"^__device__ [^\n;]*\b%s\([^;{]*\) \{" % helper, text, re.M)]
+        assert defined == ["ai_cells.inc"], (helper, defined)
+    kernels = {name: re.search(r"void %s\(.*?\n\}" % name, sources[f], re.S).group(0)
+               for name, f in (("kq_knn_avg", "ai_prep.hip"), ("kf_knn_avg", "ai_finish.hip"), ("kp_nn1", "ai_points.hip"),
+                               ("kf_nn1", "ai_finish.hip"))}
+    want = (pc.K["SLACK_ULPS"], pc.K["STOP_ULPS"])
+    for name, body in kernels.items():
+        cell, best = (r"g\.cell", "kth") if name.endswith("knn_avg") else ("cell", "best")
+        assert pc.stop_constants(body, cell, best, name) == want, name
+        assert body.count("axis_mag(") == 3 and body.count("face_gap(") == 3, name
+    loops = [kernels[name][kernels[name].index("  double best[K];"):] for name in ("kq_knn_avg", "kf_knn_avg")]
     assert loops[0] == loops[1], "the search bodies of kq_knn_avg and kf_knn_avg differ"
+    # kf_nn1 reads its chunk's slice of the cell tables (cs, ce) and speaks of major rows; nothing else may differ
+    nn1 = [kernels[name][kernels[name].index("  int cx, cy, cz;"):kernels[name].index("lb) break;")] for name in ("kp_nn1", "kf_nn1")]
+    nn1 = [re.sub(r"\s*//[^\n]*", "", body) for body in nn1]
+    assert nn1[0] == nn1[1].replace("cs[cc]", "cstart[cc]").replace("ce[cc]", "cend[cc]"), "the search bodies of kp_nn1 and kf_nn1 differ"
 
 
 def test_template_boundaries_are_fixtures():

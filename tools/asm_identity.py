@@ -1,11 +1,19 @@
 #!/usr/bin/env python3
-"""Do two builds hold the same kernel code?  Compares the gfx950 assembly that `hipcc -save-temps` leaves (*-hip-amdgcn-*.s) function
-by function -- body and `.amdhsa_*` descriptor block -- after dropping comments and the numbers of local labels, whatever the order
-of the functions and whichever file of a side holds them.  A refactor that only moves code must come out with 0 different.
+"""Do two builds hold the same kernel code?  Compares the gfx950 assembly that `hipcc -save-temps` (or `--cuda-device-only -S`) leaves
+function by function -- body and `.amdhsa_*` descriptor block -- after dropping comments, the numbers of local labels and the
+function's own name, whatever the order of the functions and whichever file of a side holds them.  A refactor that only moves code
+must come out with 0 different.
 
     hipcc <CXXFLAGS of csrc/Makefile> -save-temps -c ai_ncut.hip      (in each tree, in a scratch directory)
-    python tools/asm_identity.py OLD.s[,OLD2.s...] NEW.s[,NEW2.s...]  -> DIFF / ONLY-OLD / ONLY-NEW lines, exit status 1 on a DIFF"""
+    python tools/asm_identity.py [--rename OLD=NEW ...] OLD.s[,OLD2.s...] NEW.s[,NEW2.s...]
+
+Lines: DIFF (exit status 1), SWAP (same length, same mnemonics, the only differing lines have the two source operands of a commutative
+instruction exchanged: the same bits; counted per mnemonic, exit status 0), ONLY-OLD / ONLY-NEW for a kernel of the project's
+anonymous namespace that one side lacks.  `--rename OLD=NEW` (names as these lines print them) compares a kernel that the old side
+calls OLD with the one the new side calls NEW."""
 import re, sys, subprocess
+
+COMMUTATIVE = re.compile(r'^[vs]_(add|mul|and|or|xor|xnor|min|max)(_|$)')
 
 def funcs(path):
     out, name, buf = {}, None, []
@@ -24,6 +32,7 @@ def funcs(path):
         l = re.sub(r'BB\d+_(\d+)', r'BB#_\1', line)
         l = re.sub(r'\.Lfunc_(begin|end)\d+', r'.Lfunc_\1#', l)
         l = re.sub(r'\.Ltmp\d+', '.Ltmp#', l)
+        l = l.replace(name, '<self>')  # a renamed kernel differs in nothing but this
         l = re.sub(r'\s+', ' ', l).strip()
         if l:
             buf.append(l)
@@ -37,23 +46,67 @@ def load(spec):
     return d
 
 def dem(n):
-    return re.sub(r'\(anonymous namespace\)::', '', subprocess.run(['c++filt', n], capture_output=True, text=True).stdout.strip()).split('(')[0]
+    s = re.sub(r'\(anonymous namespace\)::', '', subprocess.run(['c++filt', n], capture_output=True, text=True).stdout.strip()).split('(')[0]
+    return s[5:] if s.startswith('void ') else s  # an instance of a template is printed with its return type
 
-old, new = load(sys.argv[1]), load(sys.argv[2])
-ours = lambda n: re.search(r'GLOBAL__N_1\d+f?k_', n) is not None
-same = diff = 0
+def swaps(vo, vn):
+    """None unless the bodies differ only by exchanged source operands of commutative instructions; else {mnemonic: lines}."""
+    if len(vo) != len(vn):
+        return None
+    count = {}
+    for a, b in zip(vo, vn):
+        if a == b:
+            continue
+        (ma, _, ra), (mb, _, rb) = a.partition(' '), b.partition(' ')
+        oa, ob = ra.split(', '), rb.split(', ')
+        if ma != mb or not COMMUTATIVE.match(ma) or len(oa) < 3 or oa[:-2] != ob[:-2] or oa[-2:] != ob[:-3:-1]:
+            return None
+        count[ma] = count.get(ma, 0) + 1
+    return count
+
+args, renames = sys.argv[1:], {}
+while args and args[0] == '--rename':
+    o, _, n = args[1].partition('=')
+    renames[o] = n
+    args = args[2:]
+old, new = load(args[0]), load(args[1])
+ours = lambda n: n.startswith('_ZN12_GLOBAL__N_1')
+by_name = {}
+for n in new:
+    by_name.setdefault(dem(n), []).append(n)
+pairs, only_old, matched = [], [], set()
 for n in sorted(set(old) | set(new)):
-    if n not in old or n not in new:
-        if ours(n):
-            print(('ONLY-OLD ' if n in old else 'ONLY-NEW ') + dem(n))
-        continue
-    for po, vo in old[n]:
-        for pn, vn in new[n]:
+    if n in old and n in new:
+        pairs.append((n, n))
+    elif n in old and ours(n):
+        targets = by_name.get(renames.get(dem(n)), [])
+        if len(targets) == 1:
+            pairs.append((n, targets[0]))
+            matched.add(targets[0])
+        else:
+            only_old.append(n)
+for n in only_old:
+    print('ONLY-OLD ' + dem(n))
+for n in sorted(new):
+    if n not in old and ours(n) and n not in matched:
+        print('ONLY-NEW ' + dem(n))
+same = diff = swapped = 0
+for no, nn in pairs:
+    label = dem(no) if no == nn else '%s -> %s' % (dem(no), dem(nn))
+    for po, vo in old[no]:
+        for pn, vn in new[nn]:
+            sw = None if vo == vn else swaps(vo, vn)
             if vo == vn:
                 same += 1
+                if no != nn:
+                    print('RENAMED', label, po.split('/')[-1], pn.split('/')[-1], 'identical')
+            elif sw is not None:
+                swapped += 1
+                print('SWAP', label, po.split('/')[-1], pn.split('/')[-1], len(vo), ' '.join('%s:%d' % kv for kv in sorted(sw.items())))
             else:
                 diff += 1
-                print('DIFF', dem(n), po.split('/')[-1], pn.split('/')[-1], len(vo), len(vn))
-nk = sum(1 for n in new if ours(n) and n in old)
-print('compared %d function pairs (%d project kernels by name): %d identical, %d different' % (same + diff, nk, same, diff))
+                print('DIFF', label, po.split('/')[-1], pn.split('/')[-1], len(vo), len(vn))
+nk = sum(1 for no, nn in pairs if ours(nn))
+print('compared %d function pairs (%d project kernels by name): %d identical, %d operand swaps only, %d different'
+      % (same + swapped + diff, nk, same, swapped, diff))
 sys.exit(1 if diff else 0)
