@@ -15,12 +15,11 @@ every output is a device tensor).  There is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _ffi
 from .config import CAM_IDS, HPR_RADIUS, MAJOR_VOXEL_SIZE, NUM_DINO_FEATURES
+from ._buffers import place_of, points_f64
 from .ncuts_api import Context, _is_device_tensor, default_context
 
 MAX_VIEWS = 64
@@ -30,6 +29,7 @@ _CAMS = ("cam2", "cam3")   # image_utils.py:103
 def transform_points(points, T):
     """open3d ``PointCloud.transform`` in a fixed order: row r of the result is ``((T[r,0]*x + T[r,1]*y) + T[r,2]*z) + T[r,3]``,
     divided by row 3 -- element-wise, each step rounded on its own (the order the device uses)."""
+    # rounds differently from `points_api._transform_points` (a matrix product) on purpose: the two stay two functions
     p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     T = np.asarray(T, dtype=np.float64)
     x, y, z = p[:, 0], p[:, 1], p[:, 2]
@@ -73,22 +73,6 @@ def hidden_point_removal(points, camera=(0.0, 0.0, 0.0), radius_factor=HPR_RADIU
     hull = ConvexHull(np.concatenate([flipped, np.zeros((1, 3))]), qhull_options="Qt")
     v = np.unique(hull.vertices)
     return v[v != p.shape[0]].astype(np.int64)
-
-
-def _f64_points(a, name):
-    if _is_device_tensor(a):
-        import torch
-        if a.dtype != torch.float64 or a.dim() != 2 or a.shape[1] != 3:
-            raise ValueError(f"{name} on the device must be a float64 (n, 3) tensor")
-        return a.contiguous()
-    if not isinstance(a, np.ndarray) and hasattr(a, "points"):
-        a = a.points
-    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
-    if a.size == 0:
-        a = a.reshape(0, 3)
-    if a.ndim != 2 or a.shape[1] != 3:
-        raise ValueError(f"{name} must be (n, 3)")
-    return a
 
 
 def _stack_maps(maps, n_views, dtype, name, on_device):
@@ -150,10 +134,11 @@ def camera_features(points, cloud, visible_indices, T_pcd2cam, K, image_hw, *, f
     """
     ctx = ctx or default_context()
     dev = _is_device_tensor(points)
-    q = _f64_points(points, "points")
-    c = _f64_points(cloud, "cloud")
+    q = points_f64(points, "points")
+    c = points_f64(cloud, "cloud")
     if dev != _is_device_tensor(c):
         raise ValueError("points and cloud must both be host arrays or both device tensors")
+    place = place_of(q)
     vis = list(visible_indices)
     V = len(vis)
     if V > MAX_VIEWS:
@@ -171,7 +156,7 @@ def camera_features(points, cloud, visible_indices, T_pcd2cam, K, image_hw, *, f
         off[v + 1] = off[v] + (int(ix.numel()) if _is_device_tensor(ix) else int(np.asarray(ix).size))
     if dev:
         import torch
-        device = q.device
+        device = place.device
         vi = (torch.cat([torch.as_tensor(np.asarray(x) if not _is_device_tensor(x) else x, device=device).reshape(-1).to(torch.int32)
                          for x in vis]) if off[-1] > 0 else torch.zeros(1, dtype=torch.int32, device=device))
         if off[-1] > 0 and (int(vi.min()) < 0 or int(vi.max()) >= M):
@@ -207,39 +192,23 @@ def camera_features(points, cloud, visible_indices, T_pcd2cam, K, image_hw, *, f
             feat = torch.as_tensor(feat, device=device)
         if sam is not None and not _is_device_tensor(sam):
             sam = torch.as_tensor(sam, device=device)
-
-        def empty(shape, dt):
-            return torch.empty(shape, dtype=dt, device=device)
-
-        def ptr(a):
-            return C.c_void_p(a.data_ptr()) if a is not None else None
-        i32, f64 = torch.int32, torch.float64
-        mem = _ffi.AI_MEM_DEVICE
-    else:
-        def empty(shape, dt):
-            return np.empty(shape, dtype=dt)
-
-        def ptr(a):
-            return a.ctypes.data if a is not None else None
-        i32, f64 = np.int32, np.float64
-        mem = _ffi.AI_MEM_HOST
+    i32, f64 = np.int32, np.float64
     if N == 0:   # nothing to compute (a device tensor of no elements has no address to pass)
-        return {"dino": empty((0, F), f64) if feature_maps is not None else None,
-                "dino_views": empty((0,), i32) if feature_maps is not None else None,
-                "sam": empty((0, V), i32) if sam_images is not None else None, "pixels": empty((0, V, 2), i32) if return_pixels else None}
-    pix = empty((N, V, 2), i32) if return_pixels else None
-    sam_out = empty((N, V), i32) if sam_images is not None else None
-    mean = empty((N, F), f64) if feature_maps is not None else None
-    views = empty((N,), i32) if feature_maps is not None else None
-    feat_p = ptr(feat) if feat is not None else (ptr(mean) if mean is not None else None)   # a non-NULL map with V = 0: never read
-    sam_p = ptr(sam) if sam is not None else (ptr(sam_out) if sam_out is not None else None)
-    if dev:
-        # every device input above (index concatenation, stacking, .contiguous() copies, uploads) was queued on torch's current
-        # stream, and the library reads them on its own stream: wait for them here, after the last of them
-        torch.cuda.current_stream(device).synchronize()
+        return {"dino": place.new((0, F), f64) if feature_maps is not None else None,
+                "dino_views": place.new((0,), i32) if feature_maps is not None else None,
+                "sam": place.new((0, V), i32) if sam_images is not None else None,
+                "pixels": place.new((0, V, 2), i32) if return_pixels else None}
+    pix = place.new((N, V, 2), i32) if return_pixels else None
+    sam_out = place.new((N, V), i32) if sam_images is not None else None
+    mean = place.new((N, F), f64) if feature_maps is not None else None
+    views = place.new((N,), i32) if feature_maps is not None else None
+    feat_p = place.addr(feat if feat is not None else mean)   # a non-NULL map with V = 0: never read
+    sam_p = place.addr(sam if sam is not None else sam_out)
+    # every device input above (index concatenation, stacking, .contiguous() copies, uploads) was queued on torch's current stream
+    place.sync()
     status = _ffi.load().ai_camera_project(
-        ctx._h, ptr(q), N, ptr(c), M, ptr(vi), off.ctypes.data, V, T.ctypes.data, Kh.ctypes.data, h, w, float(max_dist),
-        feat_p, fh or 0, fw or 0, F or 0, sam_p, mem, ptr(pix), ptr(sam_out), ptr(mean), ptr(views))
+        ctx._h, place.addr(q), N, place.addr(c), M, place.addr(vi), off.ctypes.data, V, T.ctypes.data, Kh.ctypes.data, h, w, float(max_dist),
+        feat_p, fh or 0, fw or 0, F or 0, sam_p, place.mem, place.addr(pix), place.addr(sam_out), place.addr(mean), place.addr(views))
     if status == -1 and "feature cell out of range" in _ffi.load().ai_last_error().decode("utf-8", "replace"):
         raise IndexError(_ffi.load().ai_last_error().decode("utf-8", "replace"))
     _ffi.check(status, "ai_camera_project")
@@ -271,8 +240,8 @@ def image_based_features_per_patch(dataset, pcd, chunk_indices, chunk_nc, T_pcd2
         raise ValueError("Either sam or dino must be True")
     from .prep_api import statistical_inlier_indices
     ctx = ctx or default_context()
-    pts = _f64_points(pcd, "pcd")
-    nc_pts = _f64_points(chunk_nc, "chunk_nc")
+    pts = points_f64(pcd, "pcd")
+    nc_pts = points_f64(chunk_nc, "chunk_nc")
     N = nc_pts.shape[0]
     V = len(cam_indices)
     chunk_indices = np.asarray(chunk_indices, dtype=np.int64).reshape(-1)

@@ -21,7 +21,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import _ffi
-from .ncuts_api import Context, default_context
+from ._buffers import cat_int32, concat, grow, place_of
+from .ncuts_api import Context, _is_device_tensor, default_context
 
 OVERLAPS = [0.25, 0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8, 0.85, 0.9, 0.95]   # metrics_class.py:37
 AP_OVERLAPS = OVERLAPS[1:]                                                  # :38
@@ -45,17 +46,16 @@ def label_pairs(a, b, *, ctx: Context | None = None):
     if a.shape != b.shape:
         raise ValueError("label arrays differ in length")
     lib = _ffi.load()
-    cap = 1 << 16
-    while True:
-        pa, pb = np.empty(cap, np.int32), np.empty(cap, np.int32)
-        cnt = np.empty(cap, np.int64)
+
+    def pairs(cap):
+        pa, pb, cnt = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.int64)
         total = _ffi.C.c_int64(0)
         _ffi.check(lib.ai_label_pairs(ctx._h, a.ctypes.data, b.ctypes.data, a.shape[0], _ffi.AI_MEM_HOST, cap, pa.ctypes.data,
                                       pb.ctypes.data, cnt.ctypes.data, _ffi.C.byref(total)), "ai_label_pairs")
-        if total.value <= cap:
-            k = total.value
-            return pa[:k].copy(), pb[:k].copy(), cnt[:k].copy()
-        cap = int(total.value)
+        return total.value, (pa, pb, cnt)
+    cap = 1 << 16
+    k, (pa, pb, cnt) = grow(pairs, cap)
+    return pa[:k].copy(), pb[:k].copy(), cnt[:k].copy()
 
 
 class _Table:
@@ -314,14 +314,12 @@ def merge_map(points, instances, *, centers=None, side_length=40.0, iou_min=0.01
     order.  With ``return_table`` a fourth value, a list with one int32 array per chunk: entry ``l`` is the global id local id
     ``l`` ended with; with ``return_stats`` a last value, an (n_chunks, 4) int64 array (`MERGE_STATS`).  Device tensors in give
     device tensors out; only counts cross to the host.  Errors of M10 raise ``ValueError``."""
-    from .points_api import _concat, _is_device_tensor
     ctx = ctx or default_context()
     if not isinstance(points, (list, tuple)) or not isinstance(instances, (list, tuple)) or len(points) != len(instances):
         raise ValueError("merge_map: points and instances must be lists with one entry per chunk")
     n = len(points)
-    dev = any(_is_device_tensor(a) for a in list(points) + list(instances))
-    device = next(a.device for a in list(points) + list(instances) if _is_device_tensor(a)) if dev else None
-    xyz, off = _concat(list(points), 3, np.float64, "points", dev, device)
+    place = place_of(*points, *instances)
+    xyz, off = concat(list(points), 3, np.float64, "points", place)
     m = int(off[-1])
     parts = []
     for c, a in enumerate(instances):
@@ -343,40 +341,21 @@ def merge_map(points, instances, *, centers=None, side_length=40.0, iou_min=0.01
         cen = np.ascontiguousarray(centers, dtype=np.float64)
         if cen.shape != (n, 3):
             raise ValueError("merge_map: centers must be (n_chunks, 3)")
-    if dev:
-        import torch
-        parts = [a.to(device=device, dtype=torch.int32) if _is_device_tensor(a) else
-                 torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=device) for a in parts]
-        inst = torch.cat(parts).contiguous() if m else torch.zeros(0, dtype=torch.int32, device=device)
-        xyz = xyz.contiguous()
-        nmax = [int(a.max()) if a.numel() else 0 for a in parts] if return_table else None
-        out_p = torch.empty((max(m, 1), 3), dtype=torch.float64, device=device)
-        out_i = torch.empty(max(m, 1), dtype=torch.int32, device=device)
-        out_s = torch.empty(max(m, 1), dtype=torch.int64, device=device)
-        torch.cuda.current_stream(device).synchronize()   # the concatenations ran on torch's stream, the library reads on its own
-        mem = _ffi.AI_MEM_DEVICE
-
-        def ptr(a):
-            return _ffi.C.c_void_p(a.data_ptr()) if a.numel() else None
-    else:
-        inst = np.ascontiguousarray(np.concatenate(parts), dtype=np.int32) if n else np.zeros(0, dtype=np.int32)
-        nmax = [int(a.max()) if a.size else 0 for a in parts] if return_table else None
-        out_p, out_i, out_s = np.empty((max(m, 1), 3)), np.empty(max(m, 1), np.int32), np.empty(max(m, 1), np.int64)
-        mem = _ffi.AI_MEM_HOST
-
-        def ptr(a):
-            return a.ctypes.data if a.size else None
+    inst = cat_int32(parts, place)
+    out_p, out_i, out_s = place.new((max(m, 1), 3), np.float64), place.new(max(m, 1), np.int32), place.new(max(m, 1), np.int64)
     table = stats = None
     if return_table:
+        nmax = [int(inst[off[c]:off[c + 1]].max()) if off[c + 1] > off[c] else 0 for c in range(n)]
         goff = np.concatenate([[0], np.cumsum(np.maximum(nmax, 0), dtype=np.int64)]).astype(np.int64)
         table = np.zeros(int(goff[-1]) + 1, dtype=np.int32)
     if return_stats:
         stats = np.zeros((n, len(MERGE_STATS)), dtype=np.int64)
     n_out = _ffi.C.c_int64(0)
-    out_ptr = (lambda a: _ffi.C.c_void_p(a.data_ptr())) if dev else (lambda a: a.ctypes.data)
+    # an empty input is NULL; the outputs are never NULL
+    place.sync()
     _ffi.check(_ffi.load().ai_merge_map(
-        ctx._h, ptr(xyz), ptr(inst), off.ctypes.data, n, cen.ctypes.data if cen is not None else None, float(side_length),
-        float(iou_min), mem, out_ptr(out_p), out_ptr(out_i), out_ptr(out_s), _ffi.C.byref(n_out),
+        ctx._h, place.addr_or_null(xyz), place.addr_or_null(inst), off.ctypes.data, n, cen.ctypes.data if cen is not None else None,
+        float(side_length), float(iou_min), place.mem, place.addr(out_p), place.addr(out_i), place.addr(out_s), _ffi.C.byref(n_out),
         table.ctypes.data if table is not None else None, stats.ctypes.data if stats is not None else None, None), "ai_merge_map")
     k = int(n_out.value)
     res = [out_p[:k], out_i[:k], out_s[:k]]

@@ -23,6 +23,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _ffi
+from ._buffers import is_device_tensor as _is_device_tensor, place_of
 from .config import CONFIG, PROXIMITY_THRESHOLD, SPLIT_LIM
 
 __all__ = ["Context", "DeviceGraph", "get_affinity_matrix", "build_affinity", "normalized_cut", "ncuts",
@@ -124,24 +125,16 @@ class DeviceGraph:
             pass
 
 
-def _as_f64(a, cols=None, name="array"):
-    if a is None:
-        return None
+def _as_f64(a, cols, name, place):
+    """(n, cols) float64 at `place`: a host array is converted; a torch tensor already resident in HBM is used in place, so it
+    must be float64 and contiguous as it is."""
+    if place.device is not None:
+        if a.dtype != place.dtype(np.float64) or not a.is_contiguous() or a.dim() != 2 or (cols is not None and a.shape[1] != cols):
+            raise ValueError(f"{name} on the device must be a contiguous float64 (n, {cols or 'F'}) tensor")
+        return a
     a = np.ascontiguousarray(a, dtype=np.float64)
     if a.ndim != 2 or (cols is not None and a.shape[1] != cols):
         raise ValueError(f"{name} must be 2-D" + (f" with {cols} columns" if cols else ""))
-    return a
-
-
-def _is_device_tensor(a):
-    return a is not None and hasattr(a, "data_ptr") and bool(getattr(a, "is_cuda", False))
-
-
-def _dev_f64(a, cols, name):
-    """A torch tensor already resident in HBM: float64, contiguous, (n, cols)."""
-    import torch
-    if a.dtype != torch.float64 or not a.is_contiguous() or a.dim() != 2 or (cols is not None and a.shape[1] != cols):
-        raise ValueError(f"{name} on the device must be a contiguous float64 (n, {cols or 'F'}) tensor")
     return a
 
 
@@ -171,63 +164,54 @@ def build_affinity(points, tarl=None, dino=None, *, alpha=CONFIG["alpha"], theta
     extra_sam = sam_list[1:] if beta else []
     if theta and tarl is None:
         raise ValueError("theta != 0 needs TARL features")
-    on_dev = _is_device_tensor(points)
-    if on_dev:
-        import torch
-        pts = _dev_f64(points, 3, "points")
-        t = _dev_f64(tarl, None, "tarl") if theta else None
-        d = _dev_f64(dino, None, "dino") if gamma else None
+    place = place_of(points)
+    i32 = place.dtype(np.int32)
+    pts = _as_f64(points, 3, "points", place)
+    t = _as_f64(tarl, None, "tarl", place) if theta else None
+    d = _as_f64(dino, None, "dino", place) if gamma else None
+    sm = None
+    if place.device is not None:
         for f in (t, d):
             if f is not None and not _is_device_tensor(f):
                 raise ValueError("points are on the device, so features must be too")
-        sm = None
         if beta:
-            if not _is_device_tensor(sam) or sam.dtype != torch.int32 or not sam.is_contiguous() or sam.dim() != 2:
+            if not _is_device_tensor(sam) or sam.dtype != i32 or not sam.is_contiguous() or sam.dim() != 2:
                 raise ValueError("points are on the device, so sam must be a contiguous int32 (N, views) tensor there too")
             sm = sam
-        torch.cuda.current_stream(pts.device).synchronize()  # producers of the buffers have finished
-        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
-        mem = _ffi.AI_MEM_DEVICE
-    else:
-        pts = _as_f64(points, 3, "points")
-        t = _as_f64(tarl, None, "tarl") if theta else None
-        d = _as_f64(dino, None, "dino") if gamma else None
-        sm = None
-        if beta:
-            sm = np.ascontiguousarray(np.asarray(sam), dtype=np.int32)
-            if sm.ndim != 2:
-                raise ValueError("sam must be (N, views)")
-        ptr = lambda a: a.ctypes.data if a is not None else None
-        mem = _ffi.AI_MEM_HOST
+    elif beta:
+        sm = np.ascontiguousarray(np.asarray(sam), dtype=np.int32)
+        if sm.ndim != 2:
+            raise ValueError("sam must be (N, views)")
     n = pts.shape[0]
     for f, nm in ((t, "tarl"), (d, "dino"), (sm, "sam")):
         if f is not None and f.shape[0] != n:
             raise ValueError(f"{nm} has {f.shape[0]} rows for {n} points")
     h = C.c_void_p()
+    place.sync()   # the producers of the caller's buffers have finished
     st = _ffi.load().ai_affinity_build_sam(
-        ctx._h, ptr(pts), n, ptr(t), t.shape[1] if t is not None else 0, ptr(d), d.shape[1] if d is not None else 0,
-        ptr(sm), sm.shape[1] if sm is not None else 0, float(alpha or 0.0), float(beta or 0.0), float(gamma or 0.0),
-        float(theta or 0.0), float(radius), mem, C.byref(h))
+        ctx._h, place.addr(pts), n, place.addr(t), t.shape[1] if t is not None else 0, place.addr(d), d.shape[1] if d is not None else 0,
+        place.addr(sm), sm.shape[1] if sm is not None else 0, float(alpha or 0.0), float(beta or 0.0), float(gamma or 0.0),
+        float(theta or 0.0), float(radius), place.mem, C.byref(h))
     _ffi.check(st, "ai_affinity_build")
     graph = DeviceGraph(ctx, h)
     for c in range(max(len(extra_dino), len(extra_sam))):
         ed = extra_dino[c] if c < len(extra_dino) else None
         es = extra_sam[c] if c < len(extra_sam) else None
-        if on_dev:
-            import torch
-            ed = _dev_f64(ed, None, "dino") if ed is not None else None
-            if es is not None and (not _is_device_tensor(es) or es.dtype != torch.int32 or not es.is_contiguous()):
+        ed = _as_f64(ed, None, "dino", place) if ed is not None else None
+        if place.device is not None:
+            if es is not None and (not _is_device_tensor(es) or es.dtype != i32 or not es.is_contiguous()):
                 raise ValueError("points are on the device, so sam must be a contiguous int32 tensor there too")
-        else:
-            ed = _as_f64(ed, None, "dino") if ed is not None else None
-            es = np.ascontiguousarray(np.asarray(es), dtype=np.int32) if es is not None else None
+        elif es is not None:
+            es = np.ascontiguousarray(np.asarray(es), dtype=np.int32)
         for f, nm in ((ed, "dino"), (es, "sam")):
             if f is not None and f.shape[0] != n:
                 graph.free()
                 raise ValueError(f"{nm} has {f.shape[0]} rows for {n} points")
-        _ffi.check(_ffi.load().ai_affinity_apply_camera(ctx._h, graph._h, ptr(ed), ed.shape[1] if ed is not None else 0, ptr(es),
-                                                        es.shape[1] if es is not None else 0, float(beta if es is not None else 0.0),
-                                                        float(gamma if ed is not None else 0.0), mem), "ai_affinity_apply_camera")
+        place.sync()
+        _ffi.check(_ffi.load().ai_affinity_apply_camera(ctx._h, graph._h, place.addr(ed), ed.shape[1] if ed is not None else 0,
+                                                        place.addr(es), es.shape[1] if es is not None else 0,
+                                                        float(beta if es is not None else 0.0), float(gamma if ed is not None else 0.0),
+                                                        place.mem), "ai_affinity_apply_camera")
     return graph
 
 

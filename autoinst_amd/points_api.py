@@ -15,12 +15,11 @@ All run as HIP kernels over cell lists; there is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _ffi
 from .config import ADJACENT_FRAMES_TARL, CHUNK_SIZE, MAJOR_VOXEL_SIZE, MEAN_HEIGHT, NUM_TARL_FEATURES, TARL_NORM
+from ._buffers import cat_int32, concat, place_of, segmented
 from .ncuts_api import Context, _is_device_tensor, default_context
 
 
@@ -52,6 +51,7 @@ def tarl_pool(points_major, tarl_points, tarl_features, *, radius=MAJOR_VOXEL_SI
 
 def _transform_points(points, T):
     """open3d ``PointCloud.transform``: homogeneous 4x4 applied to every point, divided by w."""
+    # a matrix product: rounds differently from `camera_api.transform_points` (fixed order) on purpose, the two stay two functions
     p = np.asarray(points, dtype=np.float64)
     T = np.asarray(T, dtype=np.float64)
     q = p @ T[:3, :3].T + T[:3, 3]
@@ -94,52 +94,6 @@ def tarl_features_per_patch(dataset, pcd, T_pcd, center_position, tarl_indices, 
     return out
 
 
-def _rows(a, cols, dtype, name, on_dev):
-    """One contiguous (n, cols) array (host) or tensor (device) of ``dtype``; ``cols`` None: any width."""
-    if on_dev:
-        import torch
-        want = torch.float64 if dtype == np.float64 else torch.float32
-        if not _is_device_tensor(a) or a.dtype != want or a.dim() != 2 or (cols is not None and a.shape[1] != cols):
-            raise ValueError(f"{name} on the device must be {want} (n, {cols or 'F'}) tensors")
-        return a.contiguous()
-    a = np.asarray(a)
-    if a.size == 0 and a.ndim != 2:
-        a = a.reshape(0, cols or 0)
-    if a.ndim != 2 or (cols is not None and a.shape[1] != cols):
-        raise ValueError(f"{name} must be (n, {cols or 'F'}) arrays")
-    return np.ascontiguousarray(a, dtype=dtype)
-
-
-def _concat(parts, cols, dtype, name, on_dev, device):
-    """(all rows, int64 offsets with len(parts) + 1 entries) of a list of per-segment (n_s, cols) arrays or tensors.  Segments
-    without rows only count in the offsets; with no row at all the result is (0, width of the first part, or 0)."""
-    if not isinstance(parts, (list, tuple)):
-        raise ValueError(f"{name}: a list of per-segment arrays, or one array together with its offsets, is expected")
-    seq = [_rows(a, cols, dtype, name, on_dev) for a in parts]
-    off = np.zeros(len(seq) + 1, dtype=np.int64)
-    np.cumsum([int(a.shape[0]) for a in seq], out=off[1:])
-    full = [a for a in seq if a.shape[0]]
-    if len({int(a.shape[1]) for a in full}) > 1:
-        raise ValueError(f"{name}: every segment must have the same width")
-    if not full:
-        width = int(seq[0].shape[1]) if seq else (cols or 0)
-        if on_dev:
-            import torch
-            return torch.zeros((0, width), dtype=torch.float64 if dtype == np.float64 else torch.float32, device=device), off
-        return np.zeros((0, width), dtype=dtype), off
-    if on_dev:
-        import torch
-        return torch.cat(full), off
-    return np.concatenate(full), off
-
-
-def _segmented(parts, offsets, cols, dtype, name, on_dev, device):
-    """`_concat` of a list, or the caller's own concatenated array with its offsets."""
-    if offsets is None:
-        return _concat(parts, cols, dtype, name, on_dev, device)
-    return _rows(parts, cols, dtype, name, on_dev), np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-
-
 def tarl_pool_map(scan_points, scan_features, T_scan2pcd, chunk_points, boxes, scan_windows, *, radius=MAJOR_VOXEL_SIZE / 2.0,
                   return_count=False, scan_offsets=None, chunk_offsets=None, ctx: Context | None = None):
     """The TARL matrix of every chunk of a map in one device call (``ai_scan_pool``): a list with one (N_c, F) float64 array
@@ -162,11 +116,10 @@ def tarl_pool_map(scan_points, scan_features, T_scan2pcd, chunk_points, boxes, s
     ctx = ctx or default_context()
     first = scan_points if scan_offsets is not None else next(iter(scan_points), None)
     qfirst = chunk_points if chunk_offsets is not None else next(iter(chunk_points), None)
-    dev = _is_device_tensor(first) or (first is None and _is_device_tensor(qfirst))
-    device = (first if _is_device_tensor(first) else qfirst).device if dev else None
-    xyz, soff = _segmented(scan_points, scan_offsets, 3, np.float64, "scan_points", dev, device)
-    feat, foff = _segmented(scan_features, scan_offsets, None, np.float32, "scan_features", dev, device)
-    q, qoff = _segmented(chunk_points, chunk_offsets, 3, np.float64, "chunk_points", dev, device)
+    place = place_of(first if first is not None else qfirst)
+    xyz, soff = segmented(scan_points, scan_offsets, 3, np.float64, "scan_points", place)
+    feat, foff = segmented(scan_features, scan_offsets, None, np.float32, "scan_features", place)
+    q, qoff = segmented(chunk_points, chunk_offsets, 3, np.float64, "chunk_points", place)
     if not np.array_equal(soff, foff) or int(feat.shape[0]) != int(xyz.shape[0]):
         raise ValueError("scan_features: one feature row per scan point expected")
     dim = int(feat.shape[1])
@@ -187,26 +140,12 @@ def tarl_pool_map(scan_points, scan_features, T_scan2pcd, chunk_points, boxes, s
         raise ValueError("scan_windows do not fit int32")
     w = np.ascontiguousarray(w.astype(np.int32))
     nq = int(q.shape[0])
-    if dev:
-        import torch
-        out = torch.empty((nq, dim), dtype=torch.float64, device=device)
-        cnt = torch.empty((nq,), dtype=torch.int32, device=device)
-        # the concatenations above were queued on torch's current stream, and the library reads them on its own
-        torch.cuda.current_stream(device).synchronize()
-
-        def ptr(a):
-            return C.c_void_p(a.data_ptr()) if a.numel() else None
-        mem = _ffi.AI_MEM_DEVICE
-    else:
-        out = np.empty((nq, dim), dtype=np.float64)
-        cnt = np.empty((nq,), dtype=np.int32)
-
-        def ptr(a):
-            return a.ctypes.data if a.size else None
-        mem = _ffi.AI_MEM_HOST
-    _ffi.check(_ffi.load().ai_scan_pool(ctx._h, ptr(xyz), soff.ctypes.data, n_scans, T.ctypes.data, ptr(feat), dim, ptr(q),
-                                        qoff.ctypes.data, n_chunks, b.ctypes.data, w.ctypes.data, float(radius), mem, ptr(out),
-                                        ptr(cnt)), "ai_scan_pool")
+    out, cnt = place.new((nq, dim), np.float64), place.new((nq,), np.int32)
+    place.sync()
+    _ffi.check(_ffi.load().ai_scan_pool(   # this entry takes NULL for every buffer without elements, the outputs included
+        ctx._h, place.addr_or_null(xyz), soff.ctypes.data, n_scans, T.ctypes.data, place.addr_or_null(feat), dim, place.addr_or_null(q),
+        qoff.ctypes.data, n_chunks, b.ctypes.data, w.ctypes.data, float(radius), place.mem, place.addr_or_null(out),
+        place.addr_or_null(cnt)), "ai_scan_pool")
     rows = [out[qoff[c]:qoff[c + 1]] for c in range(n_chunks)]
     if return_count:
         return rows, [cnt[qoff[c]:qoff[c + 1]] for c in range(n_chunks)]
@@ -300,22 +239,6 @@ def nn1_reproject(features_to, points_to, features_from, points_from, max_radius
 FINISH_STATS = ("mean", "std", "threshold", "n_inliers", "mean_z", "z_limit")   # ai_chunk_finish's ground_stats, per chunk
 
 
-def _chunk_labels(major_labels, moff, dev, device):
-    """The group ids of all chunks' major points as one int32 buffer where the points live."""
-    parts = []
-    for c, a in enumerate(major_labels):
-        a = a.reshape(-1) if _is_device_tensor(a) else np.asarray(a).reshape(-1)
-        if int(a.shape[0]) != int(moff[c + 1] - moff[c]):
-            raise ValueError(f"major_labels[{c}] has {int(a.shape[0])} entries for {int(moff[c + 1] - moff[c])} major points")
-        parts.append(a)
-    if dev:
-        import torch
-        parts = [a.to(device=device, dtype=torch.int32) if _is_device_tensor(a) else
-                 torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=device) for a in parts]
-        return torch.cat(parts).contiguous() if parts else torch.zeros(0, dtype=torch.int32, device=device)
-    return np.ascontiguousarray(np.concatenate(parts), dtype=np.int32) if parts else np.zeros(0, dtype=np.int32)
-
-
 def finish_chunks(fine, major, major_labels, ground, *, nb_neighbors=20, std_ratio=2.0, mean_height=MEAN_HEIGHT,
                   return_stats=False, ctx: Context | None = None):
     """The tail of ``ncuts_chunk`` (``ncuts_utils.py:185-199``) for all chunks of a map in one device call
@@ -338,58 +261,44 @@ def finish_chunks(fine, major, major_labels, ground, *, nb_neighbors=20, std_rat
     n = len(ground)
     if len(fine) != n or len(major) != n or (major_labels is not None and len(major_labels) != n):
         raise ValueError("fine, major, major_labels and ground must hold one entry per chunk")
-    every = list(fine) + list(major) + list(ground)
-    dev = any(_is_device_tensor(a) for a in every)
-    device = next(a.device for a in every if _is_device_tensor(a)) if dev else None
-    f, foff = _concat(list(fine), 3, np.float64, "fine", dev, device)
-    m, moff = _concat(list(major), 3, np.float64, "major", dev, device)
-    g, goff = _concat(list(ground), 3, np.float64, "ground", dev, device)
-    lab = _chunk_labels(major_labels, moff, dev, device) if major_labels is not None else None
+    place = place_of(*fine, *major, *ground)
+    f, foff = concat(list(fine), 3, np.float64, "fine", place)
+    m, moff = concat(list(major), 3, np.float64, "major", place)
+    g, goff = concat(list(ground), 3, np.float64, "ground", place)
+    lab = None
+    if major_labels is not None:
+        parts = []
+        for c, a in enumerate(major_labels):
+            a = a.reshape(-1) if _is_device_tensor(a) else np.asarray(a).reshape(-1)
+            if int(a.shape[0]) != int(moff[c + 1] - moff[c]):
+                raise ValueError(f"major_labels[{c}] has {int(a.shape[0])} entries for {int(moff[c + 1] - moff[c])} major points")
+            parts.append(a)
+        lab = cat_int32(parts, place)
+        if lab.shape[0] == 0:
+            lab = place.new(1, np.int32)   # a call without major points: not NULL (NULL means "no labels"), never read
     nf, ng = int(foff[-1]), int(goff[-1])
-    if dev:
-        import torch
-
-        def new(shape, dtype):
-            return torch.empty(shape, dtype={np.float64: torch.float64, np.int32: torch.int32}[dtype], device=device)
-
-        def ptr(a):
-            return C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None
-        torch.cuda.current_stream(device).synchronize()   # the concatenations ran on torch's stream, the library reads on its own
-        mem = _ffi.AI_MEM_DEVICE
-    else:
-        def new(shape, dtype):
-            return np.empty(shape, dtype=dtype)
-
-        def ptr(a):
-            return a.ctypes.data if a is not None and a.size else None
-        mem = _ffi.AI_MEM_HOST
-
-    def out_ptr(a):   # an output is never NULL because it is empty: NULL means "not wanted"
-        if a is None:
-            return None
-        return C.c_void_p(a.data_ptr()) if dev else a.ctypes.data
-    nn = new(max(nf, 1), np.int32) if return_stats else None
-    dist = new(max(nf, 1), np.float64) if return_stats else None
-    avg = new(max(ng, 1), np.float64) if return_stats else None
-    keep = new(max(ng, 1), np.int32)
-    flab = new(max(nf, 1), np.int32) if lab is not None else None
-    mxyz = new((max(nf + ng, 1), 3), np.float64) if lab is not None else None
-    mlab = new(max(nf + ng, 1), np.int32) if lab is not None else None
+    nn = place.new(max(nf, 1), np.int32) if return_stats else None
+    dist = place.new(max(nf, 1), np.float64) if return_stats else None
+    avg = place.new(max(ng, 1), np.float64) if return_stats else None
+    keep = place.new(max(ng, 1), np.int32)
+    flab = place.new(max(nf, 1), np.int32) if lab is not None else None
+    mxyz = place.new((max(nf + ng, 1), 3), np.float64) if lab is not None else None
+    mlab = place.new(max(nf + ng, 1), np.int32) if lab is not None else None
     koff = np.zeros(n + 1, dtype=np.int64)
     merged_off = np.zeros(n + 1, dtype=np.int64) if lab is not None else None
     stats = np.full((n, len(FINISH_STATS)), np.nan)
-    dummy = new(1, np.int32)   # major_label of a call without major points: not NULL (NULL means "no labels"), never read
-    lab_ptr = None if lab is None else out_ptr(lab if (lab.numel() if dev else lab.size) else dummy)
+    # an empty input is NULL; an output is never NULL because it is empty: there NULL means "not wanted"
+    place.sync()
     _ffi.check(_ffi.load().ai_chunk_finish(
-        ctx._h, ptr(f), foff.ctypes.data, ptr(m), moff.ctypes.data, lab_ptr, ptr(g), goff.ctypes.data, n, int(nb_neighbors),
-        float(std_ratio), float(mean_height), mem, out_ptr(nn), out_ptr(dist), out_ptr(flab), out_ptr(avg), out_ptr(keep),
-        koff.ctypes.data, stats.ctypes.data, out_ptr(mxyz), out_ptr(mlab), merged_off.ctypes.data if merged_off is not None else None),
-        "ai_chunk_finish")
+        ctx._h, place.addr_or_null(f), foff.ctypes.data, place.addr_or_null(m), moff.ctypes.data, place.addr(lab), place.addr_or_null(g),
+        goff.ctypes.data, n, int(nb_neighbors), float(std_ratio), float(mean_height), place.mem, place.addr(nn), place.addr(dist),
+        place.addr(flab), place.addr(avg), place.addr(keep), koff.ctypes.data, stats.ctypes.data, place.addr(mxyz), place.addr(mlab),
+        merged_off.ctypes.data if merged_off is not None else None), "ai_chunk_finish")
     res = []
     for c in range(n):
         k = keep[koff[c]:koff[c + 1]]
         d = {"merged_points": None, "merged_instance": None, "fine_instance": None,
-             "ground_keep": k.long() if dev else k.astype(np.int64)}
+             "ground_keep": place.index64(k)}
         if lab is not None:
             d["merged_points"] = mxyz[merged_off[c]:merged_off[c + 1]]
             d["merged_instance"] = mlab[merged_off[c]:merged_off[c + 1]]

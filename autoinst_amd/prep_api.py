@@ -47,33 +47,8 @@ import numpy as np
 
 from . import _ffi
 from .config import CHUNK_SIZE, MAJOR_VOXEL_SIZE, MINOR_VOXEL_SIZE, OVERLAP
+from ._buffers import grow, offsets_of, place_of, points_f64
 from .ncuts_api import Context, _is_device_tensor, default_context
-
-
-def _points(points, name="points"):
-    """(n, 3) float64 contiguous array or device tensor; an object with ``.points`` (an open3d cloud) gives its points."""
-    if not _is_device_tensor(points) and hasattr(points, "points") and not isinstance(points, np.ndarray):
-        points = np.asarray(points.points)
-    if _is_device_tensor(points):
-        import torch
-        if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError(f"{name} on the device must be a float64 (n, 3) tensor")
-        return points.contiguous()
-    a = np.ascontiguousarray(points, dtype=np.float64)
-    if a.size == 0:
-        a = a.reshape(0, 3)
-    if a.ndim != 2 or a.shape[1] != 3:
-        raise ValueError(f"{name} must be (n, 3)")
-    return a
-
-
-def _call_args(pts):
-    """(pointer, mem_kind, torch-or-None) of a point buffer; waits for torch's producers of a device buffer."""
-    if _is_device_tensor(pts):
-        import torch
-        torch.cuda.current_stream(pts.device).synchronize()
-        return C.c_void_p(pts.data_ptr()), _ffi.AI_MEM_DEVICE, torch
-    return pts.ctypes.data, _ffi.AI_MEM_HOST, None
 
 
 def box_select(points, boxes, *, ctx: Context | None = None):
@@ -81,26 +56,24 @@ def box_select(points, boxes, *, ctx: Context | None = None):
     (``chunk_generation.py:134-137``).  One pass over the map for all boxes.  Returns a list of int64 arrays (device tensors
     for device points)."""
     ctx = ctx or default_context()
-    pts = _points(points)
+    pts = points_f64(points)
     b = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, 6))
     nb = b.shape[0]
     if nb == 0:
         return []
-    ptr, mem, torch = _call_args(pts)
+    place = place_of(pts)
     n = int(pts.shape[0])
     offs = np.zeros(nb + 1, dtype=np.int64)
-    total = C.c_int64(0)
     lib = _ffi.load()
-    cap = 2 * n + 1024
-    while True:
-        out = torch.empty(cap, dtype=torch.int32, device=pts.device) if torch else np.empty(cap, dtype=np.int32)
-        optr = C.c_void_p(out.data_ptr()) if torch else out.ctypes.data
-        _ffi.check(lib.ai_box_select(ctx._h, ptr, n, b.ctypes.data, nb, mem, cap, optr, offs.ctypes.data, C.byref(total)),
-                   "ai_box_select")
-        if total.value <= cap:
-            break
-        cap = int(total.value)
-    full = out[:total.value].long() if torch else out[:total.value].astype(np.int64)
+
+    def select(cap):
+        out, total = place.new(cap, np.int32), C.c_int64(0)
+        place.sync()
+        _ffi.check(lib.ai_box_select(ctx._h, place.addr(pts), n, b.ctypes.data, nb, place.mem, cap, place.addr(out), offs.ctypes.data,
+                                     C.byref(total)), "ai_box_select")
+        return total.value, out
+    total, out = grow(select, 2 * n + 1024)
+    full = place.index64(out[:total])
     return [full[offs[i]:offs[i + 1]] for i in range(nb)]
 
 
@@ -108,23 +81,17 @@ def statistical_inlier_indices(points, nb_neighbors=20, std_ratio=2.0, *, return
     """Ascending indices of the points open3d's ``remove_statistical_outlier(nb_neighbors, std_ratio)`` keeps (the rules are in
     the module docstring).  With ``return_stats``: ``(indices, avg, {"mean", "std", "threshold"})``, avg per point."""
     ctx = ctx or default_context()
-    pts = _points(points)
+    pts = points_f64(points)
     nb_neighbors = int(nb_neighbors)
     n = int(pts.shape[0])
-    ptr, mem, torch = _call_args(pts)
-    if torch:
-        keep = torch.empty(max(n, 1), dtype=torch.int32, device=pts.device)
-        avg = torch.empty(max(n, 1), dtype=torch.float64, device=pts.device)
-        kptr, aptr = C.c_void_p(keep.data_ptr()), C.c_void_p(avg.data_ptr())
-    else:
-        keep = np.empty(max(n, 1), dtype=np.int32)
-        avg = np.empty(max(n, 1), dtype=np.float64)
-        kptr, aptr = keep.ctypes.data, avg.ctypes.data
+    place = place_of(pts)
+    keep, avg = place.new(max(n, 1), np.int32), place.new(max(n, 1), np.float64)
     stats = np.full(3, np.nan)
     nk = C.c_int64(0)
-    _ffi.check(_ffi.load().ai_statistical_inliers(ctx._h, ptr, n, nb_neighbors, float(std_ratio), mem, kptr, C.byref(nk), aptr,
-                                                  stats.ctypes.data), "ai_statistical_inliers")
-    idx = keep[:nk.value].long() if torch else keep[:nk.value].astype(np.int64)
+    place.sync()
+    _ffi.check(_ffi.load().ai_statistical_inliers(ctx._h, place.addr(pts), n, nb_neighbors, float(std_ratio), place.mem, place.addr(keep),
+                                                  C.byref(nk), place.addr(avg), stats.ctypes.data), "ai_statistical_inliers")
+    idx = place.index64(keep[:nk.value])
     if not return_stats:
         return idx
     return idx, avg[:n], {"mean": float(stats[0]), "std": float(stats[1]), "threshold": float(stats[2])}
@@ -134,20 +101,15 @@ def voxel_down_sample(points, voxel_size=MAJOR_VOXEL_SIZE, *, return_trace=False
     """open3d ``voxel_down_sample(voxel_size)``: the mean point of every occupied voxel, in ascending ``(ix, iy, iz)`` order.
     With ``return_trace``: ``(points, trace)``, ``trace[i]`` = output row of input point i (int32)."""
     ctx = ctx or default_context()
-    pts = _points(points)
+    pts = points_f64(points)
     n = int(pts.shape[0])
-    ptr, mem, torch = _call_args(pts)
-    if torch:
-        out = torch.empty((max(n, 1), 3), dtype=torch.float64, device=pts.device)
-        tr = torch.empty(max(n, 1), dtype=torch.int32, device=pts.device) if return_trace else None
-        optr, tptr = C.c_void_p(out.data_ptr()), (C.c_void_p(tr.data_ptr()) if tr is not None else None)
-    else:
-        out = np.empty((max(n, 1), 3), dtype=np.float64)
-        tr = np.empty(max(n, 1), dtype=np.int32) if return_trace else None
-        optr, tptr = out.ctypes.data, (tr.ctypes.data if tr is not None else None)
+    place = place_of(pts)
+    out = place.new((max(n, 1), 3), np.float64)
+    tr = place.new(max(n, 1), np.int32) if return_trace else None
     m = C.c_int64(0)
-    _ffi.check(_ffi.load().ai_voxel_down_sample(ctx._h, ptr, n, float(voxel_size), mem, optr, C.byref(m), tptr),
-               "ai_voxel_down_sample")
+    place.sync()
+    _ffi.check(_ffi.load().ai_voxel_down_sample(ctx._h, place.addr(pts), n, float(voxel_size), place.mem, place.addr(out), C.byref(m),
+                                                place.addr(tr)), "ai_voxel_down_sample")
     res = out[:m.value]
     return (res, tr[:n]) if return_trace else res
 
@@ -159,31 +121,19 @@ def voxel_down_sample_nearest(points, voxel_size=MINOR_VOXEL_SIZE, *, return_tra
     ties to the smaller input index.  Returns ``(points_out, nearest_index)``, then ``trace`` (int32, as `voxel_down_sample`)
     with ``return_trace`` and the distances (float64) with ``return_dist``, in that order.  One sort serves both results."""
     ctx = ctx or default_context()
-    pts = _points(points)
+    pts = points_f64(points)
     n = int(pts.shape[0])
-    ptr, mem, torch = _call_args(pts)
+    place = place_of(pts)
     cap = max(n, 1)
-    if torch:
-        def new(shape, dtype):
-            return torch.empty(shape, dtype=dtype, device=pts.device)
-
-        def addr(a):
-            return C.c_void_p(a.data_ptr()) if a is not None else None
-        f64, i32 = torch.float64, torch.int32
-    else:
-        def new(shape, dtype):
-            return np.empty(shape, dtype=dtype)
-
-        def addr(a):
-            return a.ctypes.data if a is not None else None
-        f64, i32 = np.float64, np.int32
-    out, nn = new((cap, 3), f64), new(cap, i32)
-    tr = new(cap, i32) if return_trace else None
-    dist = new(cap, f64) if return_dist else None
+    out, nn = place.new((cap, 3), np.float64), place.new(cap, np.int32)
+    tr = place.new(cap, np.int32) if return_trace else None
+    dist = place.new(cap, np.float64) if return_dist else None
     m = C.c_int64(0)
-    _ffi.check(_ffi.load().ai_voxel_down_sample_nearest(ctx._h, ptr, n, float(voxel_size), mem, addr(out), C.byref(m), addr(tr),
-                                                        addr(nn), addr(dist)), "ai_voxel_down_sample_nearest")
-    res = [out[:m.value], nn[:m.value].long() if torch else nn[:m.value].astype(np.int64)]
+    place.sync()
+    _ffi.check(_ffi.load().ai_voxel_down_sample_nearest(ctx._h, place.addr(pts), n, float(voxel_size), place.mem, place.addr(out),
+                                                        C.byref(m), place.addr(tr), place.addr(nn), place.addr(dist)),
+               "ai_voxel_down_sample_nearest")
+    res = [out[:m.value], place.index64(nn[:m.value])]
     if return_trace:
         res.append(tr[:n])
     if return_dist:
@@ -206,7 +156,7 @@ def downsample_map(pcd_nonground, pcd_ground, labels, voxel_size=MINOR_VOXEL_SIZ
     missing = [k for k in LABEL_KEYS if k not in labels]
     if missing:
         raise ValueError(f"labels lacks {missing}")
-    clouds = {"ground": _points(pcd_ground, "pcd_ground"), "nonground": _points(pcd_nonground, "pcd_nonground")}
+    clouds = {"ground": points_f64(pcd_ground, "pcd_ground"), "nonground": points_f64(pcd_nonground, "pcd_nonground")}
     flat = {}
     for k in LABEL_KEYS:
         a = labels[k]
@@ -267,7 +217,7 @@ def chunks_from_pointcloud(points, T_pcd, positions, first_position, indices, la
     ``kitti_out`` (when ``labels`` is given) ``labels[...][ids][inliers]`` per chunk.  The crop of all chunks is one
     `box_select`; the filter runs per chunk on the device."""
     ctx = ctx or default_context()
-    pts = _points(points)
+    pts = points_f64(points)
     centres, centre_ids = chunk_centres(T_pcd, positions, first_position, indices, chunk_size=chunk_size, overlap=overlap)
     half = 0.5 * np.asarray(chunk_size, dtype=np.float64)
     bounds = [(c - half, c + half) for c in centres]
@@ -313,12 +263,6 @@ def chunk_and_downsample_point_clouds(pcd_nonground_minor, pcd_ground_minor, T_p
 AGGREGATE_LABEL_KINDS = ("seg", "instance", "panoptic")   # aggregate_pointcloud.py:175-182
 
 
-def _scan_offsets(lengths):
-    off = np.zeros(len(lengths) + 1, dtype=np.int64)
-    np.cumsum(np.asarray(lengths, dtype=np.int64), out=off[1:])
-    return off
-
-
 def _scan_points(scan_points, scan_offsets):
     """(xyz (M, 3) float32 contiguous array or device tensor, offsets (n_scans + 1) int64) of either input form."""
     if isinstance(scan_points, (list, tuple)):
@@ -328,7 +272,7 @@ def _scan_points(scan_points, scan_offsets):
             import torch
             if not all(_is_device_tensor(p) and p.dtype == torch.float32 and p.dim() == 2 and p.shape[1] in (3, 4) for p in scan_points):
                 raise ValueError("scans on the device must all be float32 (n, 3) or (n, 4) tensors")
-            off = _scan_offsets([int(p.shape[0]) for p in scan_points])
+            off = offsets_of([int(p.shape[0]) for p in scan_points])
             return torch.cat([p[:, :3] for p in scan_points]).contiguous(), off
         parts = []
         for k, p in enumerate(scan_points):
@@ -339,7 +283,7 @@ def _scan_points(scan_points, scan_offsets):
                 raise ValueError(f"scan {k} must be a float32 (n, 3) or (n, 4) array, as dataset.get_point_cloud returns it")
             parts.append(a[:, :3])
         xyz = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0, 3), dtype=np.float32)
-        return xyz, _scan_offsets([a.shape[0] for a in parts])
+        return xyz, offsets_of([a.shape[0] for a in parts])
     if scan_offsets is None:
         raise ValueError("one array of points needs scan_offsets=")
     off = np.ascontiguousarray(np.asarray(scan_offsets, dtype=np.int64).reshape(-1))
@@ -479,28 +423,15 @@ def _ground_planes(ctx, xyz, off, words, moving_index, rmin, rmax, distance_thre
     lives."""
     n_scans, M = off.shape[0] - 1, int(xyz.shape[0])
     n_hyp = int(num_iterations)
-    ptr, mem, torch = _call_args(xyz)
-    if torch:
-        def new(shape, dtype):
-            return torch.empty(shape, dtype=dtype, device=xyz.device)
-
-        def addr(a):
-            return C.c_void_p(a.data_ptr()) if a is not None else None
-        f64, i32, u8 = torch.float64, torch.int32, torch.uint8
-    else:
-        def new(shape, dtype):
-            return np.empty(shape, dtype=dtype)
-
-        def addr(a):
-            return a.ctypes.data if a is not None else None
-        f64, i32, u8 = np.float64, np.int32, np.uint8
-    flags, planes = new(max(M, 1), u8), new((max(n_scans, 1), 4), f64)
-    best_hyp, best_count = new(max(n_scans, 1), i32), new(max(n_scans, 1), i32)
-    counts = new((max(n_scans, 1), max(min(n_hyp, 4096), 1)), i32) if return_counts else None
+    place = place_of(xyz)
+    flags, planes = place.new(max(M, 1), np.uint8), place.new((max(n_scans, 1), 4), np.float64)
+    best_hyp, best_count = place.new(max(n_scans, 1), np.int32), place.new(max(n_scans, 1), np.int32)
+    counts = place.new((max(n_scans, 1), max(min(n_hyp, 4096), 1)), np.int32) if return_counts else None
+    place.sync()
     _ffi.check(_ffi.load().ai_ground_planes(
-        ctx._h, ptr, off.ctypes.data, n_scans, addr(words), -1 if moving_index is None else int(moving_index), rmin, rmax,
-        float(distance_threshold), n_hyp, int(seed) & 0xFFFFFFFFFFFFFFFF, int(scan_base), mem, addr(flags), addr(planes), addr(best_hyp),
-        addr(best_count), addr(counts)), "ai_ground_planes")
+        ctx._h, place.addr(xyz), off.ctypes.data, n_scans, place.addr(words), -1 if moving_index is None else int(moving_index), rmin, rmax,
+        float(distance_threshold), n_hyp, int(seed) & 0xFFFFFFFFFFFFFFFF, int(scan_base), place.mem, place.addr(flags), place.addr(planes),
+        place.addr(best_hyp), place.addr(best_count), place.addr(counts)), "ai_ground_planes")
     return flags[:M], planes[:n_scans], best_hyp[:n_scans], best_count[:n_scans], (counts[:n_scans] if return_counts else None)
 
 
@@ -527,12 +458,7 @@ def ground_planes(scan_points, *, labels=None, moving_index=None, range_min=None
     rmin, rmax = _range_args(range_min, range_max)
     flags, planes, best_hyp, best_count, counts = _ground_planes(
         ctx, xyz, off, words, moving_index, rmin, rmax, distance_threshold, num_iterations, seed, scan_base, return_counts)
-    if _is_device_tensor(flags):
-        import torch
-        flags = flags.view(torch.bool)
-    else:
-        flags = flags.view(np.bool_)
-    out = (flags, planes, best_hyp, best_count)
+    out = (flags.view(place_of(flags).dtype(np.bool_)), planes, best_hyp, best_count)
     return out + (counts,) if return_counts else out
 
 
@@ -585,42 +511,29 @@ def aggregate_scans(scan_points, poses, *, labels=None, ground=None, moving_inde
         if ground_options is not None:
             raise ValueError('ground_options goes with ground="ransac"')
         flags = _ground_flags(ground, off, xyz) if ground is not None else None
-    ptr, mem, torch = _call_args(xyz)
+    place = place_of(xyz)
     cap = max(M, 1)
-    if torch:
-        def new(shape, dtype):
-            return torch.empty(shape, dtype=dtype, device=xyz.device)
-
-        def addr(a):
-            return C.c_void_p(a.data_ptr()) if a is not None else None
-        f64, i32, u32 = torch.float64, torch.int32, torch.int32
-    else:
-        def new(shape, dtype):
-            return np.empty(shape, dtype=dtype)
-
-        def addr(a):
-            return a.ctypes.data if a is not None else None
-        f64, i32, u32 = np.float64, np.int32, np.uint32
-    out = {c: new((cap, 3), f64) for c in ("ground", "nonground")}
-    lab = {f"{k}_{c}": (new(cap, u32) if words is not None else None) for k in AGGREGATE_LABEL_KINDS for c in ("ground", "nonground")}
-    src = {c: (new(cap, i32) if return_source else None) for c in ("ground", "nonground")}
+    out = {c: place.new((cap, 3), np.float64) for c in ("ground", "nonground")}
+    lab = {f"{k}_{c}": (place.new(cap, np.uint32) if words is not None else None) for k in AGGREGATE_LABEL_KINDS for c in ("ground", "nonground")}
+    src = {c: (place.new(cap, np.int32) if return_source else None) for c in ("ground", "nonground")}
     class_off = np.zeros(2 * (n_scans + 1), dtype=np.int64)
     ng, nn = C.c_int64(0), C.c_int64(0)
+    place.sync()
     _ffi.check(_ffi.load().ai_aggregate_scans(
-        ctx._h, ptr, off.ctypes.data, n_scans, T.ctypes.data, addr(words), addr(flags), -1 if moving_index is None else int(moving_index),
-        rmin, rmax, mem, addr(out["ground"]), addr(out["nonground"]), addr(lab["seg_ground"]), addr(lab["seg_nonground"]),
-        addr(lab["instance_ground"]), addr(lab["instance_nonground"]), addr(lab["panoptic_ground"]), addr(lab["panoptic_nonground"]),
-        addr(src["ground"]), addr(src["nonground"]), class_off.ctypes.data, C.byref(ng), C.byref(nn)), "ai_aggregate_scans")
+        ctx._h, place.addr(xyz), off.ctypes.data, n_scans, T.ctypes.data, place.addr(words), place.addr(flags),
+        -1 if moving_index is None else int(moving_index), rmin, rmax, place.mem, place.addr(out["ground"]), place.addr(out["nonground"]),
+        place.addr(lab["seg_ground"]), place.addr(lab["seg_nonground"]), place.addr(lab["instance_ground"]),
+        place.addr(lab["instance_nonground"]), place.addr(lab["panoptic_ground"]), place.addr(lab["panoptic_nonground"]),
+        place.addr(src["ground"]), place.addr(src["nonground"]), class_off.ctypes.data, C.byref(ng), C.byref(nn)), "ai_aggregate_scans")
     count = {"ground": ng.value, "nonground": nn.value}
     labels_dict = {}
     for key, a in lab.items():
         if a is not None:
             a = a[:count[key.split("_")[1]]]
-            labels_dict[key] = _widen_words(a) if torch else a
+            labels_dict[key] = _widen_words(a) if place.device is not None else a
     if return_source:
         for i, c in enumerate(("ground", "nonground")):
-            s = src[c][:count[c]]
-            labels_dict[f"source_{c}"] = s.long() if torch else s.astype(np.int64)
+            labels_dict[f"source_{c}"] = place.index64(src[c][:count[c]])
             labels_dict[f"offsets_{c}"] = class_off[i * (n_scans + 1):(i + 1) * (n_scans + 1)].copy()
     return out["ground"][:ng.value], out["nonground"][:nn.value], labels_dict
 
