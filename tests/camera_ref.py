@@ -59,11 +59,12 @@ def project(p_cam, K, h, w):
 
 
 def camera_features(points, cloud, visible_indices, T_pcd2cam, K, image_hw, feature_maps=None, sam_images=None, max_dist=MAX_DIST,
-                    check_mean_rows=0, seed=0):
+                    check_mean_rows=0, seed=0, seen_fn=None):
     """The restatement of ``camera_api.camera_features`` (same returns, pixels always).  The mean is summed view after view in
     float64 and divided once; with ``check_mean_rows`` > 0 that many points (plus every point with the most views) are also
     averaged the reference's literal way -- ``np.mean(rows, axis=0)`` over the stacked non-zero rows -- and must agree bit
-    for bit (AssertionError otherwise)."""
+    for bit (AssertionError otherwise).  ``seen_fn`` replaces `seen_in_view` (tests/camera_cases.py passes rule 2 over all pairs,
+    without a tree)."""
     q = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     c = np.asarray(cloud, dtype=np.float64).reshape(-1, 3)
     N, V = q.shape[0], len(visible_indices)
@@ -81,7 +82,7 @@ def camera_features(points, cloud, visible_indices, T_pcd2cam, K, image_hw, feat
     for v in range(V):
         T = np.asarray(T_pcd2cam[v], dtype=np.float64)
         vis = np.asarray(visible_indices[v], dtype=np.int64)
-        seen = seen_in_view(transform(q, T), transform(c[vis], T), max_dist)
+        seen = (seen_fn or seen_in_view)(transform(q, T), transform(c[vis], T), max_dist)
         idx = np.where(seen)[0]
         u, vv, keep = project(transform(q[idx], T), K, h, w)
         idx, u, vv = idx[keep], u[keep].astype(np.int64), vv[keep].astype(np.int64)
