@@ -13,6 +13,8 @@
 // One wave is in flight at a time; the host never waits for the device while the pool has work.
 // Groups come out in the reference's emission order (mask side first, normalized_cut.py:57-59); no float atomics,
 // so labels are reproducible run to run.
+// Every segment also carries the heights of the cut tree (FSeg::front / path; DESIGN.md section 21) and every group records the
+// height of the boundary in front of it and the cost of the cut it was refused: ai_ncut_tree returns them, ai_ncut drops them.
 
 struct RangeAlloc {  // first-fit allocator of index ranges (stable task indices)
   std::map<int, int> fr;  // start -> length
@@ -61,6 +63,14 @@ struct FSeg {  // host record of a live segment
   int pca = 0;                // (principal-axis start) 1 + chunk while the segment is prepared without a solved ancestor and its graph kept its points; 0: not
   int restarts = 0;           // times the segment was solved again because its Ritz pair failed the true-residual test
   double prev_true = 0.0;     // the true residual that sent it back
+  // cut tree (ai_ncut_tree): the threshold at which the boundary in front of the segment's first position appears, and the largest
+  // cost among the cuts that produced the segment (a Fiedler cut costs its mcut, a split into components exactly 0); -inf at a root
+  double front = -INFINITY, path = -INFINITY;
+};
+
+struct FLeaf {  // a group: where it starts, the height of the boundary in front of it, the mcut of the cut it was refused (NaN: never solved)
+  int32_t g0;
+  double front, cost;
 };
 
 static inline int fk_nf(int n) { return (n + AI_FINE_ROWS - 1) / AI_FINE_ROWS; }
@@ -188,7 +198,7 @@ class Flow {
   std::vector<FSeg> pool;  // segments listed in the current pool lists (some may be frozen already)
   std::deque<FSeg> pend_solved;
   std::vector<FSeg> pend_multi;
-  std::vector<int32_t> leaf_starts;
+  std::vector<FLeaf> leaves;          // the groups, in the order they were found (sorted by start at the end of the call)
   std::vector<int> free_slots;
   RangeAlloc fa, ca;
   int J = 0;             // Lanczos steps launched so far
@@ -707,7 +717,7 @@ class Flow {
     return AI_OK;
   }
 
-  void leaf(int g0) { leaf_starts.push_back(g0); }
+  void leaf(int g0, double front, double cost) { leaves.push_back(FLeaf{g0, front, cost}); }
 
   // chunks whose last segment has become a group give their slab rows back; waiting chunks take them
   int retire_chunks() {
@@ -1180,6 +1190,8 @@ class Flow {
           ch.restarts = s.restarts + 1;
           ch.prev_true = r_true[i];
           ch.warm_n = s.warm_n;   // (its own harvest wrote ev2 only: warm[] at its rows is still its ancestor's)
+          ch.front = s.front;
+          ch.path = s.path;
           ccomp.push_back(ch);   // (chunk_live is counted with the other continuing children below)
           continue;
         }
@@ -1199,7 +1211,7 @@ class Flow {
         }
 #endif
         if (!r_split[i]) {
-          leaf(s.g0);
+          leaf(s.g0, s.front, r_mcut[i]);
           continue;
         }
         const int na = r_ntrue[i], nb = s.n - na;
@@ -1221,19 +1233,22 @@ class Flow {
         ch.vdelta = s.vdelta;
         ch.binary_child = true;
         ch.warm_n = s.n;   // the children start from this segment's second Ritz vector (fk_partition carries it to their rows)
+        ch.path = std::max(s.path, r_mcut[i]);  // the boundary between the two sides appears once this cut and all its ancestors do
         if (q.contA) {
           ch.g0 = s.g0;
           ch.n = na;
+          ch.front = s.front;
           cbin.push_back(ch);
         } else {
-          leaf(s.g0);
+          leaf(s.g0, s.front, NAN);
         }
         if (q.contB) {
           ch.g0 = s.g0 + na;
           ch.n = nb;
+          ch.front = ch.path;
           cbin.push_back(ch);
         } else {
-          leaf(s.g0 + na);
+          leaf(s.g0 + na, ch.path, NAN);
         }
         P2.push_back(s);
         ssv.push_back(q);
@@ -1258,6 +1273,7 @@ class Flow {
         }
 #endif
         int offp = 0;
+        const double pcomp = std::max(s.path, 0.0);  // the cut between whole components costs exactly 0
         while (ti < h_troot.size() && h_troot[ti] < s.g0 + s.n) {
           const int nc = h_tsize[ti];
           if (h_troot[ti] < s.g0 || nc <= 0 || offp + nc > s.n) {
@@ -1273,10 +1289,12 @@ class Flow {
             ch.n = nc;
             ch.warm_n = s.warm_n;     // inherited: the last solved ancestor's vector, carried through this split as well
             ch.binary_child = false;  // connected by construction
+            ch.front = offp ? pcomp : s.front;
+            ch.path = pcomp;
             ccomp.push_back(ch);
             ccont[ti] = 1;
           } else {
-            leaf(s.g0 + offp);
+            leaf(s.g0 + offp, offp ? pcomp : s.front, NAN);
           }
           offp += nc;
           ++ti;
@@ -1485,7 +1503,7 @@ class Flow {
         if (T > 0.0) {
           pend_multi.push_back(s);
         } else {
-          leaf(s.g0);
+          leaf(s.g0, s.front, NAN);
           --chunk_live[s.chunk];
         }
         continue;
@@ -1507,7 +1525,7 @@ class Flow {
     t_progress = now_ms();
     if (debug && !trace)
       fprintf(stderr, "[flow] t=%.2f J=%d nft=%d wave stage %d done: A=%zu M=%zu C=%zu pool=%zu pend=%zu/%zu leaves=%zu\n", now_ms() - t_call, J, nft, (int)wstate, wA.size(), wM.size(),
-              wC.size(), pool.size(), pend_solved.size(), pend_multi.size(), leaf_starts.size());
+              wC.size(), pool.size(), pend_solved.size(), pend_multi.size(), leaves.size());
     const double t_a0 = now_ms();
     int rc = AI_OK;
     switch (wstate) {
@@ -1528,7 +1546,7 @@ class Flow {
       if (eligible(nc, n_orig[c], split_lim))
         waiting.push_back(c);
       else if (nc > 0)
-        leaf((int)off[c]);
+        leaf((int)off[c], -INFINITY, NAN);
     }
     admit();
     wC = new_roots;
@@ -1643,7 +1661,8 @@ class Flow {
 // The recursion over one graph that holds `nchunks` independent chunks back to back (rows off[c] .. off[c+1]);
 // csr->orig holds chunk-LOCAL point ids; csr's arrays belong to the call (the recursion's even depths live in them).
 static int ncut_flow(ai_ctx* ctx, const ai_csr* csr, int nchunks, const int64_t* off, const int64_t* n_orig, double T, double split_lim,
-                     const ai_ncut_opts* opts, int32_t* const* labels_out, int32_t* n_groups, ai_ncut_stats* stats_out, double t0) {
+                     const ai_ncut_opts* opts, int32_t* const* labels_out, int32_t* n_groups, ai_ncut_stats* stats_out, double t0,
+                     double* const* cut_height = nullptr, double* const* leaf_cost = nullptr) {
   Flow F(ctx);
   struct Drain {  // whatever way the call ends, nothing of it may still be running when its workspace is rewound
     Flow& f;
@@ -1686,16 +1705,19 @@ static int ncut_flow(ai_ctx* ctx, const ai_csr* csr, int nchunks, const int64_t*
     if (hts[j + 1] > hts[j]) F.stats.ms_spmv += (double)(hts[j + 1] - hts[j]) / F.clock_khz;
   F.stats.spmv_rows = (int64_t)hw[0];
   F.stats.spmv_nnz = (int64_t)hw[1];
-  std::sort(F.leaf_starts.begin(), F.leaf_starts.end());
-  // groups of chunk c = the leaf ranges inside [off[c], off[c+1]), numbered from 0 in emission order
+  std::sort(F.leaves.begin(), F.leaves.end(), [](const FLeaf& a, const FLeaf& b) { return a.g0 < b.g0; });
+  // groups of chunk c = the leaf ranges inside [off[c], off[c+1]), numbered from 0 in emission order; the cut tree of the chunk
+  // (ai_ncut_tree) is what the leaves recorded, in the same order: cut_height[c][g], leaf_cost[c][g]
   size_t li = 0;
   int64_t total_groups = 0;
   for (int c = 0; c < nchunks; ++c) {
     int g = -1;
     const int32_t nloc = (int32_t)(off[c + 1] - off[c]);
     for (int64_t p = off[c]; p < off[c + 1]; ++p) {
-      while (li < F.leaf_starts.size() && F.leaf_starts[li] == p) {
+      while (li < F.leaves.size() && F.leaves[li].g0 == p) {
         ++g;
+        if (cut_height && cut_height[c]) cut_height[c][g] = F.leaves[li].front;
+        if (leaf_cost && leaf_cost[c]) leaf_cost[c][g] = F.leaves[li].cost;
         ++li;
       }
       if (g < 0 || order[p] < 0 || order[p] >= nloc) {

@@ -14,6 +14,10 @@
 //                          (np.unique of the concatenated (K, 3) arrays WITHOUT axis flattens them).
 //   ai_unique_points    -- open3d's PointCloud.remove_duplicated_points() at :489: keep the first
 //                          point of every exact coordinate triple, order preserved.
+//   ai_ncut_relabel     -- the labels of a map's chunks at k thresholds from their cut trees (ai_ncut_tree,
+//                          DESIGN.md section 21): a boundary exists at T' iff its height < T', so a point's
+//                          group is the number of existing boundaries up to its leaf.
+#include <cmath>
 #include <cstring>
 
 #include "ai_labels_shared.h"
@@ -124,7 +128,108 @@ __global__ __launch_bounds__(AI_BLOCK) void km_inside(const double* __restrict__
   }
 }
 
+// ------------------------------------------------------------------ cut tree -> labels at k thresholds
+// flag[t * G + g] = 1 iff the boundary in front of group g exists at thresholds[t] (strict, as the frontier compares mcut < T)
+__global__ __launch_bounds__(AI_BLOCK) void kl_height_flags(const double* __restrict__ height, int64_t G, const double* __restrict__ thr,
+                                                            int32_t k, int32_t* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (i >= G * k) return;
+  flag[i] = (height[i % G] < thr[i / G]) ? 1 : 0;
+}
+
+// scan = exclusive scan of the flags (k * G + 1 entries).  One thread per point: its chunk by a search of off, its label checked
+// against the chunk's group count, then per threshold the existing boundaries in (first group of the chunk, its own group] -- the
+// first group's own flag (height -inf: always set) is left out.  Threads [0, n_chunks) also check the head of their chunk's
+// heights and count its groups.  write == 0: the checks alone (err: 1 = a label out of range, 2 = a head that is not -inf).
+__global__ __launch_bounds__(AI_BLOCK) void kl_relabel(const int32_t* __restrict__ labels, const int64_t* __restrict__ off, int32_t n_chunks,
+                                                       const double* __restrict__ height, const int64_t* __restrict__ goff,
+                                                       const int32_t* __restrict__ scan, int64_t G, int32_t k, int64_t N, int write,
+                                                       int32_t* __restrict__ labels_out, int32_t* __restrict__ counts,
+                                                       int32_t* __restrict__ err) {
+  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (i < n_chunks) {
+    const int64_t g0 = goff[i], g1 = goff[i + 1];
+    if (!write) {
+      if (g1 > g0 && height[g0] != -INFINITY) atomicOr(err, 2);
+    } else {
+      for (int32_t t = 0; t < k; ++t) counts[(int64_t)t * n_chunks + i] = (g1 > g0) ? scan[t * G + g1] - scan[t * G + g0 + 1] + 1 : 0;
+    }
+  }
+  if (i >= N) return;
+  const int32_t c = segment_of(off, n_chunks, i);
+  const int64_t g0 = goff[c], ng = goff[c + 1] - g0;
+  const int32_t l = labels[i];
+  if (l < 0 || l >= ng) {
+    if (!write) atomicOr(err, 1);
+    return;
+  }
+  if (!write) return;
+  for (int32_t t = 0; t < k; ++t) labels_out[t * N + i] = scan[t * G + g0 + l + 1] - scan[t * G + g0 + 1];
+}
+
 }  // namespace
+
+extern "C" int ai_ncut_relabel(ai_ctx* ctx, const int32_t* labels, const int64_t* off, int32_t n_chunks, const double* cut_height,
+                               const int64_t* goff, double T_max, const double* thresholds, int32_t k, int mem_kind, int32_t* labels_out,
+                               int32_t* n_groups_out) {
+  const char* me = "ai_ncut_relabel";
+  if (!ctx || !off || !goff || !thresholds || !n_groups_out || n_chunks < 1 || (mem_kind != AI_MEM_HOST && mem_kind != AI_MEM_DEVICE))
+    return bad_arg(me, "bad argument");
+  if (k < 1) return bad_arg(me, "k < 1 thresholds");
+  for (int32_t t = 0; t < k; ++t) {
+    if (!std::isfinite(thresholds[t])) return bad_arg(me, "a threshold is NaN or infinite");
+    if (!(thresholds[t] <= T_max)) return bad_arg(me, "a threshold lies above T_max: the tree holds no cut that expensive");
+  }
+  if (off[0] != 0 || goff[0] != 0) return bad_arg(me, "offsets do not start at 0");
+  for (int32_t c = 0; c < n_chunks; ++c)
+    if (off[c + 1] < off[c] || goff[c + 1] < goff[c]) return bad_arg(me, "offsets decrease");
+  const int64_t N = off[n_chunks], G = goff[n_chunks];
+  if (N >= ((int64_t)1 << 31) - 1 || G * k >= ((int64_t)1 << 31) - 1) return bad_arg(me, "points, or groups x thresholds, exceed the int32 range of the scan");
+  if ((N > 0 && (!labels || !labels_out)) || (G > 0 && !cut_height)) return bad_arg(me, "null label / height buffer");
+  AI_HIP(hipSetDevice(ctx->device));
+  ArenaScope arena_scope(&ctx->arena);
+  hipStream_t st = ctx->stream;
+  DevBuf<int32_t> own_l, own_out, flag, scan_tmp, d_cnt, d_err;
+  DevBuf<double> own_h, d_thr;
+  DevBuf<int64_t> d_off, d_goff;
+  const int32_t* dl = nullptr;
+  const double* dh = nullptr;
+  int32_t* dout = nullptr;
+  if (N > 0) AI_TRY(to_device(labels, (size_t)N, mem_kind, own_l, &dl, st));
+  if (G > 0) AI_TRY(to_device(cut_height, (size_t)G, mem_kind, own_h, &dh, st));
+  if (N > 0) AI_TRY(dev_out(labels_out, (size_t)N * k, mem_kind, own_out, &dout));
+  AI_TRY(d_off.alloc((size_t)n_chunks + 1));
+  AI_TRY(d_goff.alloc((size_t)n_chunks + 1));
+  AI_TRY(d_thr.alloc((size_t)k));
+  AI_HIP(hipMemcpyAsync(d_off.p, off, ((size_t)n_chunks + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  AI_HIP(hipMemcpyAsync(d_goff.p, goff, ((size_t)n_chunks + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  AI_HIP(hipMemcpyAsync(d_thr.p, thresholds, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st));
+  AI_TRY(flag.alloc((size_t)G * k + 1));
+  AI_TRY(d_cnt.alloc((size_t)n_chunks * k));
+  AI_TRY(d_err.alloc(1));
+  AI_HIP(hipMemsetAsync(d_err.p, 0, sizeof(int32_t), st));
+  const unsigned grid = grid_for(std::max<int64_t>(N, n_chunks));
+  hipLaunchKernelGGL(kl_relabel, dim3(grid), dim3(AI_BLOCK), 0, st, dl, (const int64_t*)d_off.p, n_chunks, dh, (const int64_t*)d_goff.p,
+                     (const int32_t*)nullptr, G, k, N, 0, (int32_t*)nullptr, (int32_t*)nullptr, d_err.p);
+  AI_KERNEL_CHECK();
+  int32_t err = 0;
+  AI_HIP(hipMemcpyAsync(&err, d_err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  AI_HIP(hipStreamSynchronize(st));
+  if (err & 2) return bad_arg(me, "the heights of a chunk do not start with -inf");
+  if (err & 1) return bad_arg(me, "a label lies outside its chunk's groups");
+  if (G > 0) {
+    hipLaunchKernelGGL(kl_height_flags, dim3(grid_for(G * k)), dim3(AI_BLOCK), 0, st, dh, G, (const double*)d_thr.p, k, flag.p);
+    AI_KERNEL_CHECK();
+  }
+  AI_TRY(scan_flags(st, flag.p, G * k, scan_tmp));
+  hipLaunchKernelGGL(kl_relabel, dim3(grid), dim3(AI_BLOCK), 0, st, dl, (const int64_t*)d_off.p, n_chunks, dh, (const int64_t*)d_goff.p,
+                     (const int32_t*)flag.p, G, k, N, 1, dout, d_cnt.p, d_err.p);
+  AI_KERNEL_CHECK();
+  if (mem_kind != AI_MEM_DEVICE) AI_TRY(to_caller(labels_out, (const int32_t*)dout, (size_t)N * k, mem_kind, st));
+  AI_HIP(hipMemcpyAsync(n_groups_out, d_cnt.p, (size_t)n_chunks * k * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  AI_HIP(hipStreamSynchronize(st));
+  return AI_OK;
+}
 
 extern "C" int ai_label_pairs(ai_ctx* ctx, const int32_t* a, const int32_t* b, int64_t n, int mem_kind, int64_t cap, int32_t* pair_a,
                               int32_t* pair_b, int64_t* pair_count, int64_t* n_pairs) {

@@ -23,11 +23,12 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _ffi
-from ._buffers import is_device_tensor as _is_device_tensor, place_of
+from ._buffers import HOST, Place, cat_int32, is_device_tensor as _is_device_tensor, offsets_of, place_of
 from .config import CONFIG, PROXIMITY_THRESHOLD, SPLIT_LIM
 
 __all__ = ["Context", "DeviceGraph", "get_affinity_matrix", "build_affinity", "normalized_cut", "ncuts",
-           "ncuts_labels", "ncuts_labels_batch", "ncuts_chunk", "default_context", "last_stats"]
+           "ncuts_labels", "ncuts_labels_batch", "ncuts_chunk", "default_context", "last_stats",
+           "CutTree", "ncuts_tree", "ncuts_tree_batch", "relabel", "normalized_cut_sweep"]
 
 
 class Context:
@@ -281,6 +282,164 @@ def ncuts_labels_batch(graphs, num_points_orig=None, T=CONFIG["T"], split_lim=SP
     _last_stats = stats.as_dict()   # filled on AI_ERR_NO_CONVERGENCE too (`last_stats()` after the exception)
     _ffi.check(status, "ai_ncut_batch")
     return labs, [int(x) for x in ng], _last_stats
+
+
+# --------------------------------------------------------------------------- cut tree: every threshold from one cut
+def _check_threshold(T, T_max, what="T"):
+    T = float(T)
+    if not np.isfinite(T):
+        raise ValueError(f"{what} = {T} is not a finite threshold")
+    if T > T_max:
+        raise ValueError(f"{what} = {T} lies above T_max = {T_max}: the tree holds no cut that expensive (cut again at a larger T_max)")
+    return T
+
+
+class CutTree:
+    """The recursion of one chunk at ``T_max``, flat (``ai_ncut_tree``).
+
+    ``labels`` / ``n_groups`` are what `ncuts_labels` returns at ``T_max``.  ``cut_height[g]`` (g >= 1) is the threshold above which
+    the boundary between groups g - 1 and g exists: the largest cost among the cut that made it and that cut's ancestors (a Fiedler
+    cut costs its mcut, a split into connected components 0.0); ``cut_height[0]`` is -inf.  ``leaf_cost[g]`` is the mcut of the cut
+    group g was refused (>= T_max, +inf where the sweep found none, NaN where the group was never solved), so ``min(leaf_cost)`` is
+    the smallest threshold above ``T_max`` at which the partition would change.  Any ``T <= T_max`` is answered from these arrays;
+    the comparison is strict as in the cut itself (a boundary of height h is absent at T = h), and T <= 0 gives one group."""
+
+    def __init__(self, labels, n_groups, cut_height, leaf_cost, T_max, ctx: Context | None = None):
+        self.labels = labels
+        self.n_groups = int(n_groups)
+        self.cut_height = np.ascontiguousarray(cut_height, dtype=np.float64)
+        self.leaf_cost = None if leaf_cost is None else np.ascontiguousarray(leaf_cost, dtype=np.float64)
+        self.T_max = float(T_max)
+        self.ctx = ctx
+        if self.cut_height.ndim != 1 or self.cut_height.shape[0] != self.n_groups:
+            raise ValueError(f"cut_height has shape {self.cut_height.shape} for {self.n_groups} groups")
+        if self.n_groups and self.cut_height[0] != -np.inf:
+            raise ValueError("cut_height[0] must be -inf")
+
+    def n_groups_at(self, T) -> int:
+        T = _check_threshold(T, self.T_max)
+        return int(np.count_nonzero(self.cut_height < T)) if self.n_groups else 0
+
+    def labels_at(self, T):
+        """The labels `ncuts_labels` gives at ``T`` (int32, where ``labels`` lives), computed on the device from the tree."""
+        _check_threshold(T, self.T_max)
+        return relabel([self], [T])[0][0][0]
+
+    def groups_at(self, T, ids=None):
+        """The partition at ``T`` in the form `normalized_cut` returns: a list of arrays of ``ids`` (default: row numbers)."""
+        lab = self.labels_at(T)
+        if _is_device_tensor(lab):
+            lab = lab.cpu().numpy()
+        ids = np.arange(lab.shape[0]) if ids is None else np.asarray(ids)
+        if ids.shape[0] != lab.shape[0]:
+            raise ValueError(f"ids has {ids.shape[0]} entries for {lab.shape[0]} points")
+        return _groups_from_labels(lab, self.n_groups_at(T), ids)
+
+
+def ncuts_tree(graph: DeviceGraph, num_points_orig: int, T_max: float, split_lim: float = SPLIT_LIM, *,
+               tol=None, max_iter=None, check_every=None, time_spmv=False, ctx: Context | None = None) -> CutTree:
+    """`ncuts_labels` at ``T_max`` that keeps what the recursion learned: a `CutTree`, which answers every T <= T_max.
+    The statistics of the call are `last_stats()`."""
+    global _last_stats
+    ctx = ctx or graph.ctx
+    lab = np.empty(graph.n, dtype=np.int32)
+    hgt = np.empty(graph.n, dtype=np.float64)
+    cst = np.empty(graph.n, dtype=np.float64)
+    ng = C.c_int32()
+    stats = _ffi.NcutStats()
+    o = _opts(tol, max_iter, check_every, time_spmv)
+    status = _ffi.load().ai_ncut_tree(ctx._h, graph._h, int(num_points_orig), float(T_max), float(split_lim), C.byref(o),
+                                      lab.ctypes.data, C.byref(ng), hgt.ctypes.data, cst.ctypes.data, C.byref(stats))
+    _last_stats = stats.as_dict()
+    _ffi.check(status, "ai_ncut_tree")
+    g = int(ng.value)
+    return CutTree(lab, g, hgt[:g].copy(), cst[:g].copy(), T_max, ctx)
+
+
+def ncuts_tree_batch(graphs, num_points_orig=None, T_max=CONFIG["T"], split_lim=SPLIT_LIM, *, tol=None, max_iter=None,
+                     check_every=None, time_spmv=False, window_rows=None, ctx: Context | None = None):
+    """`ncuts_labels_batch` at ``T_max`` that returns one `CutTree` per chunk (``ai_ncut_tree_batch``); each is what `ncuts_tree`
+    gives for its chunk alone.  The statistics of the call are `last_stats()`."""
+    global _last_stats
+    graphs = list(graphs)
+    if not graphs:
+        return []
+    ctx = ctx or graphs[0].ctx
+    k = len(graphs)
+    norig = [g.n for g in graphs] if num_points_orig is None else [int(x) for x in num_points_orig]
+    labs = [np.empty(g.n, dtype=np.int32) for g in graphs]
+    hgts = [np.empty(max(g.n, 1), dtype=np.float64) for g in graphs]
+    csts = [np.empty(max(g.n, 1), dtype=np.float64) for g in graphs]
+    gh = (C.c_void_p * k)(*[g._h for g in graphs])
+    lp = (C.c_void_p * k)(*[a.ctypes.data for a in labs])
+    hp = (C.c_void_p * k)(*[a.ctypes.data for a in hgts])
+    cp = (C.c_void_p * k)(*[a.ctypes.data for a in csts])
+    no = (C.c_int64 * k)(*norig)
+    ng = (C.c_int32 * k)()
+    stats = _ffi.NcutStats()
+    o = _opts(tol, max_iter, check_every, time_spmv, window_rows)
+    status = _ffi.load().ai_ncut_tree_batch(ctx._h, gh, k, no, float(T_max), float(split_lim), C.byref(o), lp, ng, hp, cp, C.byref(stats))
+    _last_stats = stats.as_dict()
+    _ffi.check(status, "ai_ncut_tree_batch")
+    return [CutTree(labs[c], ng[c], hgts[c][:ng[c]].copy(), csts[c][:ng[c]].copy(), T_max, ctx) for c in range(k)]
+
+
+def relabel(trees, thresholds, device=None, *, ctx: Context | None = None):
+    """The labels of several chunks at several thresholds from their trees, in one device call (``ai_ncut_relabel``).
+
+    ``trees``: `CutTree`s (their labels host arrays, or int32 tensors on one GPU); ``thresholds``: finite values <= every tree's
+    ``T_max``.  ``device``: a torch device to upload host labels to and leave the results on (default: where the labels live).
+    Returns ``(labels, n_groups)``: ``labels[t][c]`` is chunk c's label array at ``thresholds[t]`` (a view of one buffer per
+    threshold), ``n_groups[t, c]`` its number of groups there."""
+    trees = list(trees)
+    if not trees or not all(isinstance(t, CutTree) for t in trees):
+        raise ValueError("relabel: a non-empty list of CutTree objects is expected")
+    thr = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, dtype=np.float64)))
+    if thr.ndim != 1 or thr.shape[0] < 1:
+        raise ValueError("relabel: at least one threshold is expected")
+    t_max = min(t.T_max for t in trees)
+    for x in thr:
+        _check_threshold(x, t_max, "threshold")
+    place = place_of(*[t.labels for t in trees]) if device is None else Place(device)
+    for t in trees:
+        if place.device is None and _is_device_tensor(t.labels):
+            raise ValueError("relabel: labels on the host and on a device are mixed")
+    ctx = ctx or next((t.ctx for t in trees if t.ctx is not None), None) or default_context()
+    lab = cat_int32([t.labels for t in trees], place)
+    off = offsets_of([int(t.labels.shape[0]) for t in trees])
+    goff = offsets_of([t.n_groups for t in trees])
+    hgt = np.concatenate([t.cut_height for t in trees]) if goff[-1] else np.zeros(0, dtype=np.float64)
+    if place.device is not None:
+        import torch
+        hgt = torch.as_tensor(hgt, device=place.device)
+    n, k, nc = int(off[-1]), int(thr.shape[0]), len(trees)
+    out = place.new((k, n), np.int32)
+    counts = np.empty((k, nc), dtype=np.int32)
+    mem = place.mem
+    place.sync()
+    _ffi.check(_ffi.load().ai_ncut_relabel(ctx._h, place.addr_or_null(lab), off.ctypes.data, nc, place.addr_or_null(hgt), goff.ctypes.data,
+                                           float(t_max), thr.ctypes.data, k, mem, place.addr_or_null(out), counts.ctypes.data),
+               "ai_ncut_relabel")
+    return [[out[t, off[c]:off[c + 1]] for c in range(nc)] for t in range(k)], counts
+
+
+def normalized_cut_sweep(w, num_points_orig, labels, Ts, split_lim=0.01, *, ctx: Context | None = None, tol=None, max_iter=None):
+    """`normalized_cut` at every threshold of ``Ts`` for the cost of the one at ``max(Ts)``: ``{T: list[np.ndarray]}``."""
+    labels = np.asarray(labels)
+    Ts = [float(T) for T in Ts]
+    if not Ts or not all(np.isfinite(T) for T in Ts):
+        raise ValueError("normalized_cut_sweep: Ts must be a non-empty list of finite thresholds")
+    own = not isinstance(w, DeviceGraph)
+    g = DeviceGraph.from_scipy(w, ctx) if own else w
+    try:
+        if labels.shape[0] != g.n:
+            raise ValueError(f"labels has {labels.shape[0]} entries for a {g.n}-row matrix")
+        tree = ncuts_tree(g, int(num_points_orig), max(Ts), split_lim, tol=tol, max_iter=max_iter)
+    finally:
+        if own:
+            g.free()
+    labs, counts = relabel([tree], Ts)
+    return {T: _groups_from_labels(labs[t][0], int(counts[t, 0]), labels) for t, T in enumerate(Ts)}
 
 
 def _groups_from_labels(lab, ng, labels):

@@ -126,7 +126,7 @@ def gather_labels(local: dict, device=None, force: bool = False):
 
 
 def run_chunks(chunks, *, threads: int = 2, batch: int = 12, device: int | None = None, alpha=None, theta=None, gamma=None,
-               T=None, split_lim=None, contexts=None, builders: int = 1):
+               T=None, split_lim=None, contexts=None, builders: int = 1, tree: bool = False):
     """The chunk loop of ``run_pipeline.py:160-179`` for the chunks of ONE rank / GPU.
 
     ``chunks``: sequence of ``(points, tarl)`` or ``(points, tarl, dino)`` (host arrays or device tensors; ``tarl`` / ``dino``
@@ -139,6 +139,9 @@ def run_chunks(chunks, *, threads: int = 2, batch: int = 12, device: int | None 
     `Context` each; 0: none) build the affinity graphs of the NEXT batches while the cuts run, at most ``threads`` batches ahead
     (`bench.py` measures this arrangement: +3 % over every thread building its own batch first).  A failure in any batch is raised
     after the other threads have finished their current batch.
+
+    ``tree=True``: ``T`` is the largest threshold of interest (``T_max``) and the result is one `ncuts_api.CutTree` per chunk
+    instead of its label array: `ncuts_api.relabel` then gives the labels at any ``T' <= T`` without another cut.
     """
     import queue
     import threading
@@ -213,7 +216,12 @@ def run_chunks(chunks, *, threads: int = 2, batch: int = 12, device: int | None 
                         return
                     build(ids, ctxs[w], graphs)
                 # the cut runs on THIS thread's context whichever context built the graphs (a context serves one thread at a time)
-                if len(graphs) == 1:
+                if tree:
+                    labs = api.ncuts_tree_batch(graphs, [sizes[i] for i in ids], T, split_lim, ctx=ctxs[w])
+                    if own:
+                        for t in labs:
+                            t.ctx = None   # (the context is closed when this function returns)
+                elif len(graphs) == 1:
                     lab, _, _ = api.ncuts_labels(graphs[0], sizes[ids[0]], T, split_lim, ctx=ctxs[w])
                     labs = [lab]
                 else:

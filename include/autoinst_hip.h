@@ -203,6 +203,39 @@ int ai_ncut_batch(ai_ctx* ctx, const ai_csr* const* graphs, int32_t count, const
                   int32_t* n_groups, ai_ncut_stats* stats);
 
 /*
+ * The cut tree of a chunk: one cut at T_max that also answers every threshold T' <= T_max.  A segment is
+ * split iff its best cut costs less than T, and neither the eligibility of a segment nor its solve depends on T, so the recursion
+ * at T' is a prefix of the recursion at T_max.  The groups are position ranges of one array, in emission order, so the tree is flat:
+ *   cut_height[g], g >= 1: the threshold above which the boundary between group g - 1 and group g exists -- the LARGEST cost among
+ *     the cut that made the boundary and that cut's ancestors (costs are not monotone down the tree).  A Fiedler cut costs its mcut,
+ *     a split into connected components exactly 0.0.  cut_height[0] = -inf.
+ *   leaf_cost[g]: the mcut of the cut group g itself was refused (>= T_max; +inf where the sweep found none); NaN where the group
+ *     was never solved (not eligible, or a disconnected segment under T_max <= 0).  The smallest one is the smallest threshold
+ *     above T_max at which the partition would change.
+ *   The group of point i at T' <= T_max is #{ j in [1, labels[i]] : cut_height[j] < T' } (strict, as the device compares);
+ *   T' <= 0 leaves one group per chunk.
+ * ai_ncut_tree / ai_ncut_tree_batch behave as ai_ncut / ai_ncut_batch with T = T_max (same labels, bit for bit) and fill
+ * cut_height / leaf_cost (HOST arrays of capacity graphs[c]->n per chunk; leaf_cost may be NULL) wherever those fill the labels,
+ * on AI_ERR_NO_CONVERGENCE too.
+ *
+ * ai_ncut_relabel: the labels at k thresholds from the trees of n_chunks chunks, in one call.  labels: the chunks' labels
+ *   concatenated (off: HOST, n_chunks + 1); cut_height: their heights concatenated (goff: HOST, n_chunks + 1; chunk c has
+ *   goff[c + 1] - goff[c] groups); thresholds: HOST, k values.  labels_out[t * N + i] (N = off[n_chunks]) is point i's group at
+ *   thresholds[t], n_groups_out[t * n_chunks + c] (HOST) the number of chunk c's groups there.  labels, cut_height and labels_out
+ *   are host or device per mem_kind.  AI_ERR_BAD_ARG, with no output written, for k < 1, a NaN or infinite threshold, a threshold
+ *   above T_max, cut_height[goff[c]] != -inf, or a label outside [0, goff[c + 1] - goff[c]).  Chunks without points are allowed.
+ */
+int ai_ncut_tree(ai_ctx* ctx, const ai_csr* csr, int64_t num_points_orig, double T_max, double split_lim,
+                 const ai_ncut_opts* opts, int32_t* labels_out, int32_t* n_groups, double* cut_height, double* leaf_cost,
+                 ai_ncut_stats* stats);
+int ai_ncut_tree_batch(ai_ctx* ctx, const ai_csr* const* graphs, int32_t count, const int64_t* num_points_orig,
+                       double T_max, double split_lim, const ai_ncut_opts* opts, int32_t* const* labels_out,
+                       int32_t* n_groups, double* const* cut_height, double* const* leaf_cost, ai_ncut_stats* stats);
+int ai_ncut_relabel(ai_ctx* ctx, const int32_t* labels, const int64_t* off, int32_t n_chunks, const double* cut_height,
+                    const int64_t* goff, double T_max, const double* thresholds, int32_t k, int mem_kind,
+                    int32_t* labels_out, int32_t* n_groups_out);
+
+/*
  * Building blocks exposed for parity tests (top-level call of the recursion only).  These run the
  * legacy Solver kernels (k_lz_* / k_sweep), NOT the ai_ncut / ai_ncut_batch path: the values of the
  * path that ships are pinned per segment by the test-only dump (tests/test_gpu_flow_values.py).
