@@ -20,7 +20,8 @@ def __getattr__(name):
                 "chunk_and_downsample_point_clouds", "voxel_down_sample_nearest", "downsample_map"):
         from . import prep_api as _p
         return getattr(_p, name)
-    if name in ("camera_features", "image_based_features_per_patch", "hidden_point_removal", "masks_to_image"):
+    if name in ("camera_features", "image_based_features_per_patch", "hidden_point_removal", "masks_to_image",
+                "hidden_point_removal_device", "visible_sets"):
         from . import camera_api as _c
         return getattr(_c, name)
     raise AttributeError(name)

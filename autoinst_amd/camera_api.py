@@ -8,6 +8,9 @@
   per-view host steps (poses, hidden point removal, the crop and the inlier intersection) stay in Python, the per-point search,
   projection and gathers run in one `camera_features` call per camera;
 * `hidden_point_removal` -- open3d 0.17 ``PointCloud::HiddenPointRemoval`` restated on the host over scipy's qhull;
+* `hidden_point_removal_device`, `visible_sets` -- the same visible sets on the device, one linear program in two unknowns per
+  point instead of a hull (``csrc/ai_hidden.hip``; rules H1-H6 in ``include/autoinst_hip.h``), all views of
+  a chunk in one call;
 * `masks_to_image` -- ``image_utils.py:44-52``.
 
 Inputs are NumPy arrays; `camera_features` also takes float64 torch tensors on the context's GPU (then every array input and
@@ -19,7 +22,7 @@ import numpy as np
 
 from . import _ffi
 from .config import CAM_IDS, HPR_RADIUS, MAJOR_VOXEL_SIZE, NUM_DINO_FEATURES
-from ._buffers import place_of, points_f64
+from ._buffers import cat_int32, place_of, points_f64
 from .ncuts_api import Context, _is_device_tensor, default_context
 
 MAX_VIEWS = 64
@@ -73,6 +76,68 @@ def hidden_point_removal(points, camera=(0.0, 0.0, 0.0), radius_factor=HPR_RADIU
     hull = ConvexHull(np.concatenate([flipped, np.zeros((1, 3))]), qhull_options="Qt")
     v = np.unique(hull.vertices)
     return v[v != p.shape[0]].astype(np.int64)
+
+
+def visible_sets(cloud, T_pcd2cam, *, subset=None, radius_factor=HPR_RADIUS, return_stats=False, ctx: Context | None = None):
+    """The points of ``cloud`` visible from the camera of each of V views, on the device (`ai_hidden_points`): per view the
+    ascending int64 rows of ``cloud``, or None for a view the removal skips (fewer than 4 points, all points equal, a
+    coordinate that is not finite, or a sphere that does not hold the points: where `hidden_point_removal` raises, the
+    reference's "hpr skip").  One library call serves all views.
+
+    cloud (M, 3): points in the pcd frame, a NumPy array or a float64 tensor on the context's GPU (then the index arrays are
+    device tensors too); T_pcd2cam: V 4x4 transforms (last row 0 0 0 1); subset: rows of ``cloud`` the removal is run on (the
+    reference's ``bound_indices``), all rows when None.  With ``return_stats`` the result is ``(sets, stats)``, ``stats`` (V, 4)
+    int64: points the local pass proved hidden, re-solves summed over the points, most re-solves of one point, points at the camera.
+    """
+    ctx = ctx or default_context()
+    c = points_f64(cloud, "cloud")
+    place = place_of(c)
+    T = np.ascontiguousarray(np.asarray(T_pcd2cam, dtype=np.float64).reshape(-1, 4, 4))
+    V, M = int(T.shape[0]), int(c.shape[0])
+    sub = None
+    if subset is not None:
+        on_dev = _is_device_tensor(subset)
+        if on_dev and place.device is None:
+            raise ValueError("subset on the device needs the cloud on the device too")
+        sub64 = subset.reshape(-1) if on_dev else np.asarray(subset).reshape(-1)
+        if int(sub64.shape[0]) and (int(sub64.min()) < 0 or int(sub64.max()) >= M):
+            raise IndexError("subset holds a row outside the cloud")
+        sub = cat_int32([sub64], place)
+    m = M if sub is None else int(sub.shape[0])
+    flags = place.new((V, m), np.uint8)
+    counts, status, stats = np.zeros(V, dtype=np.int64), np.zeros(V, dtype=np.int32), np.zeros((V, 4), dtype=np.int64)
+    mem = place.mem
+    place.sync()
+    code = _ffi.load().ai_hidden_points(ctx._h, place.addr_or_null(c), M, place.addr_or_null(sub), m, T.ctypes.data, V, float(radius_factor),
+                                        mem, place.addr_or_null(flags), counts.ctypes.data, status.ctypes.data, stats.ctypes.data)
+    _ffi.check(code, "ai_hidden_points")
+    sets = []
+    for v in range(V):
+        if status[v]:
+            sets.append(None)
+            continue
+        if place.device is None:
+            local = np.flatnonzero(flags[v]).astype(np.int64)
+            sets.append(local if sub is None else sub[local].astype(np.int64))
+        else:
+            local = flags[v].nonzero().reshape(-1)
+            sets.append(local if sub is None else place.index64(sub[local]))
+        if int(sets[-1].shape[0]) != int(counts[v]):
+            raise RuntimeError(f"ai_hidden_points: view {v} has {int(sets[-1].shape[0])} flags set, its count says {int(counts[v])}")
+    return (sets, stats) if return_stats else sets
+
+
+def hidden_point_removal_device(points, camera=(0.0, 0.0, 0.0), radius_factor=HPR_RADIUS, *, ctx: Context | None = None):
+    """`hidden_point_removal` on the device: the ascending int64 indices of the points visible from ``camera`` (a NumPy array
+    for a NumPy array, a device tensor for a float64 device tensor).  Raises ValueError where the removal skips the cloud
+    (`visible_sets`), as the host function raises there."""
+    T = np.eye(4)
+    T[:3, 3] = -np.asarray(camera, dtype=np.float64).reshape(3)   # row r of the fixed-order transform: (1 * x + 0 + 0) - camera_r
+    visible = visible_sets(points, T[None], radius_factor=radius_factor, ctx=ctx)[0]
+    if visible is None:
+        raise ValueError("hidden_point_removal_device: fewer than 4 points, no extent, a coordinate that is not finite, or a "
+                         "sphere that does not hold the points")
+    return visible
 
 
 def _stack_maps(maps, n_views, dtype, name, on_device):
@@ -217,7 +282,7 @@ def camera_features(points, cloud, visible_indices, T_pcd2cam, K, image_hw, *, f
 
 def image_based_features_per_patch(dataset, pcd, chunk_indices, chunk_nc, T_pcd2world, cam_indices, hpr_masks=None, sam=True,
                                    dino=True, rm_perp=0.0, pcd_chunk=None, vis=False, *, cam_ids=CAM_IDS, dino_mean=False,
-                                   ctx: Context | None = None):
+                                   hpr="qhull", ctx: Context | None = None):
     """Drop-in for ``image_based_features_per_patch`` (``image_utils.py:89-360``): the same positional arguments and return forms
     -- ``(point2sam_list, point2dino_list)``, ``point2sam_list``, or ``(point2dino_list, visibility_mask)`` for sam and dino /
     sam only / dino only -- with ``point2sam`` (N, V) int64 (-1: no label) and ``point2dino`` (N, V, F) float64 per camera.
@@ -229,6 +294,8 @@ def image_based_features_per_patch(dataset, pcd, chunk_indices, chunk_nc, T_pcd2
     ``get_pose(0)``-transformed coordinates lie strictly inside the chunk's bounds (:158-179, formed once, not per view); a view
     is skipped when the removal raises ("hpr skip") or when no visible point is a chunk inlier ("out of view skip").  The
     visibility mask is all zeros, as with ``vis=False``.  ``rm_perp`` and ``vis=True`` are not implemented.
+    ``hpr`` chooses the removal when ``hpr_masks`` is None: "qhull" (the default) is `hidden_point_removal` on the host, view by
+    view; "device" is one `visible_sets` call per camera with ``bound_indices`` as its subset, a skipped view being an "hpr skip".
     ``dataset`` needs ``get_image(cam, 0).size``, ``get_pose``, ``get_calibration_matrices``, ``get_sam_mask`` and
     ``get_dinov2_features``; ``pcd`` / ``chunk_nc`` are arrays or objects with ``.points``.
     """
@@ -238,6 +305,8 @@ def image_based_features_per_patch(dataset, pcd, chunk_indices, chunk_nc, T_pcd2
         raise NotImplementedError("vis=True is not implemented")
     if not sam and not dino:
         raise ValueError("Either sam or dino must be True")
+    if hpr not in ("qhull", "device"):
+        raise ValueError('hpr must be "qhull" or "device"')
     from .prep_api import statistical_inlier_indices
     ctx = ctx or default_context()
     pts = points_f64(pcd, "pcd")
@@ -263,12 +332,24 @@ def image_based_features_per_patch(dataset, pcd, chunk_indices, chunk_nc, T_pcd2
         cam = _CAMS[cam_id]
         width, height = dataset.get_image(cam, 0).size
         kept, Ts, rows, Ks = [], [], [], []
-        for i, points_index in enumerate(cam_indices):
+
+        def view(points_index):
             T_lidar2world = np.asarray(dataset.get_pose(points_index), dtype=np.float64)
             T_lidar2cam, K = dataset.get_calibration_matrices(cam)
-            T_pcd2cam = (np.asarray(T_lidar2cam, dtype=np.float64) @ np.linalg.inv(T_lidar2world)) @ np.asarray(T_pcd2world,
-                                                                                                                dtype=np.float64)
-            if hpr_masks is None:
+            return (np.asarray(T_lidar2cam, dtype=np.float64) @ np.linalg.inv(T_lidar2world)) @ np.asarray(T_pcd2world,
+                                                                                                           dtype=np.float64), K
+
+        device_sets = None
+        if hpr_masks is None and hpr == "device" and V:   # one call needs every view's transform; the host paths ask view by view
+            views = [view(points_index) for points_index in cam_indices]
+            device_sets = visible_sets(pts, np.array([T for T, _ in views]), subset=bound_indices, radius_factor=HPR_RADIUS, ctx=ctx)
+        for i, points_index in enumerate(cam_indices):
+            T_pcd2cam, K = views[i] if device_sets is not None else view(points_index)
+            if device_sets is not None:
+                if device_sets[i] is None:   # "hpr skip"
+                    continue
+                visible = np.asarray(device_sets[i])
+            elif hpr_masks is None:
                 try:
                     local = hidden_point_removal(transform_points(pts[bound_indices], T_pcd2cam), camera=(0, 0, 0),
                                                  radius_factor=HPR_RADIUS)

@@ -602,6 +602,52 @@ int ai_ground_planes(ai_ctx* ctx, const float* scan_xyz, const int64_t* scan_off
                      int32_t* best_count, int32_t* hyp_count);
 
 /*
+ * Hidden point removal of V views in one call: open3d 0.17 PointCloud::HiddenPointRemoval as hidden_point_removal_o3d calls it
+ * (pipeline/utils/image/hidden_points_removal.py:6-25) inside image_based_features_per_patch (pipeline/utils/image/image_utils.py:
+ * 155-204), without a hull: one linear program in two unknowns per point.  cloud_xyz: M points in the pcd
+ * frame; subset (may be NULL: all M points, m = M): m rows of the cloud, the reference's bound_indices; T_pcd2cam: V transforms.
+ *   H1 Transform.  Point j of the subset goes to the camera frame of view v by rule R1 of ai_scan_pool (fixed order, no
+ *      contraction).  A last row of T other than (0, 0, 0, 1), or an entry that is not finite, is AI_ERR_BAD_ARG for the call.
+ *   H2 Sphere.  D = sqrt((dx*dx + dy*dy) + dz*dz) of the extent of the view's points, R = radius_factor * D, S = (2R) * (2R).
+ *      d_j = sqrt((x*x + y*y) + z*z); d_j == 0 counts as 1e-4 with direction 0 (the host function's rule).  e_j = p_j / d_j
+ *      (three divisions), r_j = 2R - d_j, u_j = S / r_j.  The flipped point is r_j e_j; the origin is appended.
+ *   H3 Constraint.  Point i is a vertex of the flipped hull iff some t in the plane orthogonal to e_i satisfies, for every j,
+ *      t . w_ij <= g_ij with c = (ex_i*ex_j + ey_i*ey_j) + ez_i*ez_j -- exactly 1 when e_j equals e_i in all three components --
+ *      w = e_j - c * e_i, g = u_j - c * u_i (4R^2 times 1/r_j - c/r_i).  In the basis a = (e_i x axis) / |e_i x axis|, axis the
+ *      unit axis of the smallest |component| of e_i (the lower axis on a tie), b = e_i x a, the constraint reads
+ *      t0 * A0 + t1 * A1 <= g with A0 = (wx*ax + wy*ay) + wz*az, A1 = (wx*bx + wy*by) + wz*bz.  Every product, sum, quotient and
+ *      square root is rounded on its own.  The boundary is feasible: two equal points are both visible (0 <= 0), a point straight
+ *      behind a nearer one is hidden (w = 0, g < 0).  The constraint of i itself is 0 <= 0.
+ *   H4 Decision.  Seidel's incremental program over a list of constraints, from a start t: the first constraint k of the list,
+ *      after the last one re-solved, with t0*A0 + t1*A1 > g is re-solved: nn = A0*A0 + A1*A1 (nn == 0: infeasible), f = (t.A - g)
+ *      / nn, p = t - A * f, dir = (-A1, A0); every earlier constraint j of the list, and the four of the box |t_k| <= 1e12, gives
+ *      den = A_j . dir, num = g_j - A_j . p; den > 0: hi = min(hi, num / den); den < 0: lo = max(lo, num / den); den == 0 and
+ *      num < 0: infeasible.  lo > hi: infeasible.  Else t = p + min(max(0, lo), hi) * dir.  min and max are exact, so the order
+ *      in which a re-solve visits the earlier constraints does not matter.
+ *   H5 Lists.  The view's points are sorted (stable) by the cell of e_j in the fixed grid of 64^3 cells over [-1, 1]^3 (cell index
+ *      min(max(floor((e + 1) * 32), 0), 63) per axis, key (cz * 64 + cy) * 64 + cx).  Local pass, from t = 0: the points of i's
+ *      own cell, then of the 26 cells around it in (dz, dy, dx) order, each cell in sorted order; an infeasible list proves i
+ *      hidden.  Global pass, from the local pass's t: all points in sorted order.  i is visible iff both lists are feasible.
+ *      A point at the camera (d_i == 0 before the replacement) coincides with the appended origin and is not visible: this is
+ *      this project's own rule (the reference's hull has the origin and such a point as one location and defines no flag for it).
+ *      The global pass may pass over records that cannot be violated at its t (a proven bound): H4 does
+ *      nothing at a constraint that is not violated, so the result is that of the plain scan bit for bit.
+ *   H6 Skipped views.  Fewer than 4 points, R not positive (all points equal), S not finite, a coordinate that is not finite in
+ *      the camera frame, or a sphere that does not hold the points (far >= 2R, far = sqrt((fx*fx + fy*fy) + fz*fz) of the largest
+ *      |coordinate| per axis, so that every r_j of a computed view is positive; a small cloud far from the camera with a small
+ *      radius_factor): status_out[v] = 1, the view's flags and count are not written, the call goes on (the reference's "hpr
+ *      skip": open3d raises there).  status_out[v] = 0 for a computed view.
+ * flags_out (V x m, one byte per point, 1 = visible) and count_out (V) depend on nothing but the view's own points: a view gives
+ * the same bytes alone or among others.  stats_out (may be NULL): V x 4 -- points settled by the local pass, re-solves summed over
+ * the points, the largest number of re-solves of one point, points at the camera.  AI_ERR_BAD_ARG: m or M outside [0, 2^30),
+ * V < 0, a subset row outside [0, M), radius_factor not finite.  cloud_xyz, subset and flags_out are host or device per mem_kind;
+ * T_pcd2cam (V x 16 row-major), count_out, status_out and stats_out are HOST arrays.
+ */
+int ai_hidden_points(ai_ctx* ctx, const double* cloud_xyz, int64_t n_cloud, const int32_t* subset, int64_t n_subset,
+                     const double* T_pcd2cam, int32_t n_views, double radius_factor, int mem_kind, uint8_t* flags_out,
+                     int64_t* count_out, int32_t* status_out, int64_t* stats_out);
+
+/*
  * Timing hook for bench.py: runs `reps` fused Lanczos SpMV steps on the whole graph as
  * one segment and returns the average kernel time (HIP events on the context's stream)
  * plus the algorithmic byte count of one launch.
