@@ -24,4 +24,7 @@ def __getattr__(name):
                 "hidden_point_removal_device", "visible_sets"):
         from . import camera_api as _c
         return getattr(_c, name)
+    if name in ("dbscan", "clusters_dbscan", "clusterize_pcd", "keep_largest_labels"):
+        from . import cluster_api as _d
+        return getattr(_d, name)
     raise AttributeError(name)

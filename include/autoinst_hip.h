@@ -648,6 +648,32 @@ int ai_hidden_points(ai_ctx* ctx, const double* cloud_xyz, int64_t n_cloud, cons
                      int64_t* count_out, int32_t* status_out, int64_t* stats_out);
 
 /*
+ * DBSCAN of n_clouds clouds in one call: sklearn.cluster.DBSCAN(eps, min_samples).fit(cloud).labels_ for every cloud, as
+ * AggregationClustering.clusters_hdbscan / clusterize_pcd run it on the non-ground points (pipeline/utils/aggregate.py:253-327),
+ * label for label.  xyz: the concatenated clouds, off[n_clouds] points; cloud c is rows off[c] .. off[c + 1]
+ * and may be empty.  Indices below are rows of xyz.
+ *   D1 Neighbour.  j is a neighbour of i iff both are in the same cloud and (dx*dx + dy*dy) + dz*dz <= eps*eps, every product
+ *      and sum rounded on its own (no contraction), eps*eps rounded once, the test inclusive.  i is its own neighbour; points
+ *      with equal coordinates count once each.
+ *   D2 Core.  i is a core point iff it has at least min_samples neighbours.  count_out[i] = min(neighbours, min_samples): the
+ *      count is saturated, the search stops where the answer is known.
+ *   D3 Clusters.  The clusters are the connected components of the core points under D1.
+ *   D4 Numbering.  Within a cloud the clusters are numbered 0, 1, ... in ascending order of their smallest core index.
+ *   D5 Border and noise.  A point that is not core takes the smallest cluster number among its core neighbours; with no core
+ *      neighbour its label is -1.  It joins one cluster and connects none.
+ *   D6 Independence.  A cloud's outputs are the same bits whatever other clouds share the call, wherever its points lie and
+ *      whatever cell size the search grid ended up with: they are a function of D1 on the cloud's own points alone.
+ * labels (one int32 per point), n_clusters (one per cloud), count_out (may be NULL), sizes_out (may be NULL; as long as labels:
+ * the size of cluster k of cloud c at off[c] + k, border points included, the rest of the cloud's stretch 0).  Sizes are integer
+ * sums: two calls are bit-identical.  AI_ERR_BAD_ARG: eps (or eps*eps) not positive or not finite; min_samples < 1; off not
+ * starting at 0 or decreasing; 2^30 points or more; a coordinate that is not finite.  No point at all (off[n_clouds] == 0) is not
+ * an error: every n_clusters is 0.  xyz, labels, count_out and sizes_out are host or device per mem_kind; off (n_clouds + 1) and
+ * n_clusters are HOST arrays.
+ */
+int ai_dbscan(ai_ctx* ctx, const double* xyz, const int64_t* off, int32_t n_clouds, double eps, int32_t min_samples,
+              int mem_kind, int32_t* labels, int32_t* n_clusters, int32_t* count_out, int32_t* sizes_out);
+
+/*
  * Timing hook for bench.py: runs `reps` fused Lanczos SpMV steps on the whole graph as
  * one segment and returns the average kernel time (HIP events on the context's stream)
  * plus the algorithmic byte count of one launch.
