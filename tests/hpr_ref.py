@@ -90,8 +90,9 @@ _BOX1 = np.array([0.0, 0.0, 1.0, -1.0])
 _BOXG = np.full(4, BOX)
 
 
-def seidel(A0, A1, g, t0, t1):
-    """H4 over the list (A0, A1, g) from the start (t0, t1): (feasible, t0, t1, re-solves)."""
+def seidel(A0, A1, g, t0, t1, trace=None):
+    """H4 over the list (A0, A1, g) from the start (t0, t1): (feasible, t0, t1, re-solves).  ``trace`` (a list) receives the list
+    position of every re-solve, the infeasible one included."""
     t0, t1 = F(t0), F(t1)
     n, pos, nres = g.shape[0], 0, 0
     with np.errstate(all="ignore"):
@@ -101,6 +102,8 @@ def seidel(A0, A1, g, t0, t1):
                 break
             k = pos + int(np.argmax(viol))
             nres += 1
+            if trace is not None:
+                trace.append(k)
             ok, t0, t1 = _resolve(A0, A1, g, t0, t1, k)
             if not ok:
                 return False, t0, t1, nres
@@ -236,8 +239,9 @@ def skip_audit(p_cam, radius_factor, variant="rule"):
     return met, passed, unsound, changed
 
 
-def _seidel_range(A0, A1, g, t0, t1, a, b):
-    """`seidel` over positions a .. b - 1 of the list, the earlier constraints being all positions below the violated one."""
+def _seidel_range(A0, A1, g, t0, t1, a, b, trace=None):
+    """`seidel` over positions a .. b - 1 of the list, the earlier constraints being all positions below the violated one.
+    ``trace`` (a list) receives the position of every re-solve, the infeasible one included."""
     pos = a
     with np.errstate(all="ignore"):
         while pos < b:
@@ -245,6 +249,8 @@ def _seidel_range(A0, A1, g, t0, t1, a, b):
             if not viol.any():
                 break
             k = pos + int(np.argmax(viol))
+            if trace is not None:
+                trace.append(k)
             ok, t0, t1 = _resolve(A0, A1, g, t0, t1, k)
             if not ok:
                 return False, t0, t1, 0
