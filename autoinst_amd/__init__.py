@@ -8,8 +8,8 @@ from .config import CONFIG, CONFIG_SPATIAL, CONFIG_TARL_SPATIAL, CONFIG_TARL_SPA
 
 def __getattr__(name):
     # compute entry points load the HIP library on first use and raise if it is missing
-    if name in ("normalized_cut", "ncuts", "get_affinity_matrix", "build_affinity", "ncuts_chunk", "ncuts_labels", "ncuts_labels_batch",
-                "Context", "DeviceGraph", "default_context", "last_stats", "fiedler", "sweep", "lsym_apply", "bench_spmv", "eigs_smallest",
+    if name in ("normalized_cut", "ncuts", "get_affinity_matrix", "build_affinity", "build_affinity_batch", "ncuts_chunk", "ncuts_labels",
+                "ncuts_labels_batch", "Context", "DeviceGraph", "default_context", "last_stats", "fiedler", "sweep", "lsym_apply", "bench_spmv", "eigs_smallest",
                 "CutTree", "ncuts_tree", "ncuts_tree_batch", "relabel", "normalized_cut_sweep"):
         from . import ncuts_api as _n
         return getattr(_n, name)

@@ -129,30 +129,18 @@ __device__ __forceinline__ double dist3(double ax, double ay, double az, double 
 // the neighbours within the radius; FILL = true writes their ids and distances.  (One thread per point walking the ~115
 // candidates serially took 0.16 + 0.24 ms per 200k-point chunk.)
 #define AI_NB_LANES 8
+// the walk of one row: `c` is the row's linear cell in a grid of nx * ny * nz cells whose ranges are cstart / cend; returns the
+// number of neighbours.  The single build passes its one grid, the batched build the grid of the row's chunk (its cell tables
+// offset to that chunk's cells), so both visit a row's candidates in the same order.
 template <bool FILL>
-__global__ __launch_bounds__(AI_BLOCK) void k_neighbours(const double* __restrict__ X, const double* __restrict__ Y,
-                                                         const double* __restrict__ Z, const int32_t* __restrict__ cellid,
-                                                         const int32_t* __restrict__ cstart, const int32_t* __restrict__ cend,
-                                                         int64_t n, Grid g, double radius, int32_t* __restrict__ cnt,
-                                                         const int32_t* __restrict__ rowptr, int32_t* __restrict__ col,
-                                                         double* __restrict__ dist, int32_t* __restrict__ stash_col,
-                                                         double* __restrict__ stash_dist, int stash_cap,
-                                                         const int32_t* __restrict__ cnt_in) {
-  // FILL = false with a stash: the counting pass also keeps the first stash_cap hits of every row (ids + distances, row p at
-  // p * stash_cap), so that filling the CSR is a copy (k_nb_unstash) instead of a second walk; FILL = true with cnt_in: only
-  // the rows with more than stash_cap neighbours are walked again.
-  const int64_t gid = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  const int64_t p = gid / AI_NB_LANES;
-  const int l = (int)(gid % AI_NB_LANES);
-  const int sub = (threadIdx.x & 63) / AI_NB_LANES;  // which group of the wave
-  const bool live = p < n && !(FILL && cnt_in != nullptr && cnt_in[p < n ? p : 0] <= stash_cap);
-  // every lane of the wave runs the same loops (ballots need the whole wave); a dead group simply finds nothing
-  const int64_t pp = live ? p : n - 1;
-  const double x = X[pp], y = Y[pp], z = Z[pp];
-  const int32_t c = cellid[pp];
-  const int cx = c % g.nx, cy = (c / g.nx) % g.ny, cz = c / (g.nx * g.ny);
+__device__ __forceinline__ int32_t nb_walk(const double* __restrict__ X, const double* __restrict__ Y, const double* __restrict__ Z,
+                                           const int32_t* __restrict__ cstart, const int32_t* __restrict__ cend, const int nx,
+                                           const int ny, const int nz, const bool live, const int64_t p, const int l, const int sub,
+                                           const double x, const double y, const double z, const int32_t c, const double radius,
+                                           const int32_t base, int32_t* __restrict__ col, double* __restrict__ dist,
+                                           int32_t* __restrict__ stash_col, double* __restrict__ stash_dist, const int stash_cap) {
+  const int cx = c % nx, cy = (c / nx) % ny, cz = c / (nx * ny);
   int32_t k = 0;
-  const int32_t base = (FILL && live) ? rowptr[p] : 0;
   for (int dz = -1; dz <= 1; ++dz) {
     const int zz = cz + dz;
     for (int dy = -1; dy <= 1; ++dy) {
@@ -165,9 +153,9 @@ __global__ __launch_bounds__(AI_BLOCK) void k_neighbours(const double* __restric
       for (int half = 0; half < 2; ++half) {
         const int xa = (cx & 1) ? (half == 0 ? cx - 1 : cx + 1) : (half == 0 ? cx - 1 : cx);
         const int xb = (cx & 1) ? (half == 0 ? cx : cx + 1) : (half == 0 ? cx - 1 : cx + 1);
-        const bool row_in = live && zz >= 0 && zz < g.nz && yy >= 0 && yy < g.ny;
-        const bool ina = row_in && xa >= 0 && xa < g.nx, inb = row_in && xb != xa && xb >= 0 && xb < g.nx;
-        const int32_t rowc = row_in ? (zz * g.ny + yy) * g.nx : 0;
+        const bool row_in = live && zz >= 0 && zz < nz && yy >= 0 && yy < ny;
+        const bool ina = row_in && xa >= 0 && xa < nx, inb = row_in && xb != xa && xb >= 0 && xb < nx;
+        const int32_t rowc = row_in ? (zz * ny + yy) * nx : 0;
         const int32_t sa = ina ? cstart[rowc + xa] : -1, sb = inb ? cstart[rowc + xb] : -1;
         const int32_t ea = (ina && sa >= 0) ? cend[rowc + xa] : 0, eb = (inb && sb >= 0) ? cend[rowc + xb] : 0;
         const int32_t s = (sa >= 0) ? sa : (sb >= 0 ? sb : 0);
@@ -204,6 +192,33 @@ __global__ __launch_bounds__(AI_BLOCK) void k_neighbours(const double* __restric
       }
     }
   }
+  return k;
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(AI_BLOCK) void k_neighbours(const double* __restrict__ X, const double* __restrict__ Y,
+                                                         const double* __restrict__ Z, const int32_t* __restrict__ cellid,
+                                                         const int32_t* __restrict__ cstart, const int32_t* __restrict__ cend,
+                                                         int64_t n, Grid g, double radius, int32_t* __restrict__ cnt,
+                                                         const int32_t* __restrict__ rowptr, int32_t* __restrict__ col,
+                                                         double* __restrict__ dist, int32_t* __restrict__ stash_col,
+                                                         double* __restrict__ stash_dist, int stash_cap,
+                                                         const int32_t* __restrict__ cnt_in) {
+  // FILL = false with a stash: the counting pass also keeps the first stash_cap hits of every row (ids + distances, row p at
+  // p * stash_cap), so that filling the CSR is a copy (k_nb_unstash) instead of a second walk; FILL = true with cnt_in: only
+  // the rows with more than stash_cap neighbours are walked again.
+  const int64_t gid = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  const int64_t p = gid / AI_NB_LANES;
+  const int l = (int)(gid % AI_NB_LANES);
+  const int sub = (threadIdx.x & 63) / AI_NB_LANES;  // which group of the wave
+  const bool live = p < n && !(FILL && cnt_in != nullptr && cnt_in[p < n ? p : 0] <= stash_cap);
+  // every lane of the wave runs the same loops (ballots need the whole wave); a dead group simply finds nothing
+  const int64_t pp = live ? p : n - 1;
+  const double x = X[pp], y = Y[pp], z = Z[pp];
+  const int32_t c = cellid[pp];
+  const int32_t base = (FILL && live) ? rowptr[p] : 0;
+  const int32_t k = nb_walk<FILL>(X, Y, Z, cstart, cend, g.nx, g.ny, g.nz, live, p, l, sub, x, y, z, c, radius, base, col, dist,
+                                  stash_col, stash_dist, stash_cap);
   if (!FILL && live && l == 0) cnt[p] = k;
 }
 
@@ -702,6 +717,71 @@ static int upload_if_host(const double* src, size_t count, int mem_kind, DevBuf<
   return AI_OK;
 }
 
+// The cell grid of one cloud from its bounding box (cell = radius, a hair wider).  0: fine; 1: the box is not finite; 2: more than
+// 1023 cells on an axis (ext = extent / cell); 3: more than 2^28 cells.  One definition, so that the batched build gives every chunk
+// the grid the single build gives it.
+static int affinity_grid(const double mn[3], const double mx[3], double radius, Grid& g, int64_t& ncell, double ext[3]) {
+  for (int a = 0; a < 3; ++a)
+    if (!(mn[a] <= mx[a]) || !(mx[a] - mn[a] < 1e15)) return 1;
+  const double cell = radius * (1.0 + 1e-9);  // a hair wider than r: neighbours are always within +-1 cell
+  g.minx = mn[0];
+  g.miny = mn[1];
+  g.minz = mn[2];
+  g.inv_cell = 1.0 / cell;
+  for (int a = 0; a < 3; ++a) ext[a] = (mx[a] - mn[a]) / cell;
+  if (ext[0] >= 1023.0 || ext[1] >= 1023.0 || ext[2] >= 1023.0) return 2;
+  g.nx = (int)floor(ext[0]) + 1;
+  g.ny = (int)floor(ext[1]) + 1;
+  g.nz = (int)floor(ext[2]) + 1;
+  ncell = (int64_t)g.nx * g.ny * g.nz;
+  return ncell > ((int64_t)1 << 28) ? 3 : 0;
+}
+
+// The feature factors of a graph whose val[] holds the spatial distances: the launch of the single build, which the batched build
+// makes on the rows of a whole group (a stored value does not depend on the tile it is computed in).
+static void launch_weights(hipStream_t st, int32_t* rowptr, int32_t* col, double* val, int32_t* orig, int64_t n, const double* d_tarl,
+                           int32_t tarl_dim, uint8_t* notarl, const double* d_dino, int32_t dino_dim, double alpha, double theta,
+                           double gamma, const int32_t* d_sam, int32_t sam_views, double beta) {
+  const unsigned gw = (unsigned)((n + (AI_BLOCK / 64) - 1) / (AI_BLOCK / 64));
+  const bool has_t = d_tarl != nullptr, has_d = d_dino != nullptr;
+  static const int force_rowwise = getenv("AI_WEIGHTS_ROWWISE") ? atoi(getenv("AI_WEIGHTS_ROWWISE")) : 0;
+  const bool tiled = !force_rowwise && (has_t || has_d) && d_sam == nullptr && (!has_t || tarl_dim % AW_SLAB == 0) && (!has_d || dino_dim % AW_SLAB == 0) &&
+                     (uint64_t)n * (uint64_t)std::max(has_t ? tarl_dim : 0, has_d ? dino_dim : 0) < ((uint64_t)1 << 33);  // staging offsets: 32 bits of 16-byte units
+  if (tiled) {
+    // LDS-tiled: every distinct neighbour's feature row is read once per 16-row tile
+    // 16-row tiles (256 threads) by default; AI_WEIGHTS_TILE=32 selects the 32-row form (512 threads: built and measured, not
+    // shipped, see README.md).  Same bits: an entry's sum does not depend on the tile it is computed in
+    // (tests/test_gpu_affinity.py compares the two forms bit for bit)
+    static const int tile16 = getenv("AI_WEIGHTS_TILE") ? atoi(getenv("AI_WEIGHTS_TILE")) != 32 : 1;
+    if (tile16)
+      hipLaunchKernelGGL((k_weights_lanes<256, 256, 32>), dim3((unsigned)((n + 15) / 16)), dim3(256), 0, st, (const int32_t*)rowptr,
+                         (const int32_t*)col, val, (const int32_t*)orig, n, d_tarl, tarl_dim, (const uint8_t*)notarl, d_dino, dino_dim,
+                         alpha, theta, gamma);
+    else
+      hipLaunchKernelGGL((k_weights_lanes<512, 384, 32>), dim3((unsigned)((n + 31) / 32)), dim3(512), 0, st, (const int32_t*)rowptr,
+                         (const int32_t*)col, val, (const int32_t*)orig, n, d_tarl, tarl_dim, (const uint8_t*)notarl, d_dino, dino_dim,
+                         alpha, theta, gamma);
+  } else {
+    // wave per row (SAM factor, widths that are not multiples of 16): the row's own features stay in registers
+    // when the width is the reference's (96-d TARL, 384-d DINO);
+    // an absent factor takes the width-0 instantiation so that it costs no registers
+    const bool t96 = d_tarl != nullptr && tarl_dim == 96, d384 = d_dino != nullptr && dino_dim == 384;
+#define AI_LAUNCH_W(TK, DK)                                                                                                        \
+  hipLaunchKernelGGL((k_weights<TK, DK>), dim3(gw), dim3(AI_BLOCK), 0, st, (const int32_t*)rowptr, (const int32_t*)col, val,        \
+                     (const int32_t*)orig, n, d_tarl, tarl_dim, (const uint8_t*)notarl, d_dino, dino_dim, alpha, theta, gamma, d_sam, \
+                     sam_views, beta, 0)
+    if (t96 && d384)
+      AI_LAUNCH_W(6, 24);
+    else if (t96)
+      AI_LAUNCH_W(6, 0);
+    else if (d384)
+      AI_LAUNCH_W(0, 24);
+    else
+      AI_LAUNCH_W(0, 0);
+#undef AI_LAUNCH_W
+  }
+}
+
 #ifdef AW_PHASES
 extern "C" int ai_debug_aw_phases(unsigned long long* out, int reset) {
   AI_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_aw_phase), sizeof(unsigned long long) * 8));
@@ -781,29 +861,21 @@ extern "C" int ai_affinity_build_sam(ai_ctx* ctx, const double* xyz, int64_t n, 
       if (hpart[b * 6 + a] < mn[a]) mn[a] = hpart[b * 6 + a];
       if (hpart[b * 6 + 3 + a] > mx[a]) mx[a] = hpart[b * 6 + 3 + a];
     }
-  for (int a = 0; a < 3; ++a)
-    if (!(mn[a] <= mx[a]) || !(mx[a] - mn[a] < 1e15)) {
+  Grid g;
+  int64_t ncell = 0;
+  double ext[3];
+  switch (affinity_grid(mn, mx, radius, g, ncell, ext)) {
+    case 1:
       ai_set_error("ai_affinity_build: coordinates are not finite");
       return AI_ERR_BAD_ARG;
-    }
-  Grid g;
-  const double cell = radius * (1.0 + 1e-9);  // a hair wider than r: neighbours are always within +-1 cell
-  g.minx = mn[0];
-  g.miny = mn[1];
-  g.minz = mn[2];
-  g.inv_cell = 1.0 / cell;
-  const double ex = (mx[0] - mn[0]) / cell, ey = (mx[1] - mn[1]) / cell, ez = (mx[2] - mn[2]) / cell;
-  if (ex >= 1023.0 || ey >= 1023.0 || ez >= 1023.0) {
-    ai_set_error("ai_affinity_build: extent / radius = (%.0f, %.0f, %.0f) exceeds 1023 cells per axis", ex, ey, ez);
-    return AI_ERR_BAD_ARG;
-  }
-  g.nx = (int)floor(ex) + 1;
-  g.ny = (int)floor(ey) + 1;
-  g.nz = (int)floor(ez) + 1;
-  const int64_t ncell = (int64_t)g.nx * g.ny * g.nz;
-  if (ncell > ((int64_t)1 << 28)) {
-    ai_set_error("ai_affinity_build: %lld grid cells exceed the dense cell-table limit", (long long)ncell);
-    return AI_ERR_BAD_ARG;
+    case 2:
+      ai_set_error("ai_affinity_build: extent / radius = (%.0f, %.0f, %.0f) exceeds 1023 cells per axis", ext[0], ext[1], ext[2]);
+      return AI_ERR_BAD_ARG;
+    case 3:
+      ai_set_error("ai_affinity_build: %lld grid cells exceed the dense cell-table limit", (long long)ncell);
+      return AI_ERR_BAD_ARG;
+    default:
+      break;
   }
 
   const unsigned gb = (unsigned)((n + AI_BLOCK - 1) / AI_BLOCK);
@@ -924,47 +996,9 @@ extern "C" int ai_affinity_build_sam(ai_ctx* ctx, const double* xyz, int64_t n, 
     hipLaunchKernelGGL(k_zero_rows, dim3(gz), dim3(AI_BLOCK), 0, st, d_tarl, tarl_dim, A->orig, n, notarl.p);
     AI_HIPF(hipGetLastError());
   }
-  {
-    const unsigned gw = (unsigned)((n + (AI_BLOCK / 64) - 1) / (AI_BLOCK / 64));
-    const bool has_t = d_tarl != nullptr, has_d = d_dino != nullptr;
-    static const int force_rowwise = getenv("AI_WEIGHTS_ROWWISE") ? atoi(getenv("AI_WEIGHTS_ROWWISE")) : 0;
-    const bool tiled = !force_rowwise && (has_t || has_d) && d_sam == nullptr && (!has_t || tarl_dim % AW_SLAB == 0) && (!has_d || dino_dim % AW_SLAB == 0) &&
-                       (uint64_t)n * (uint64_t)std::max(has_t ? tarl_dim : 0, has_d ? dino_dim : 0) < ((uint64_t)1 << 33);  // staging offsets: 32 bits of 16-byte units
-    if (tiled) {
-      // LDS-tiled: every distinct neighbour's feature row is read once per 16-row tile
-      // 16-row tiles (256 threads) by default; AI_WEIGHTS_TILE=32 selects the 32-row form (512 threads: built and measured, not
-      // shipped, see README.md).  Same bits: an entry's sum does not depend on the tile it is computed in
-      // (tests/test_gpu_affinity.py compares the two forms bit for bit)
-      static const int tile16 = getenv("AI_WEIGHTS_TILE") ? atoi(getenv("AI_WEIGHTS_TILE")) != 32 : 1;
-      if (tile16)
-        hipLaunchKernelGGL((k_weights_lanes<256, 256, 32>), dim3((unsigned)((n + 15) / 16)), dim3(256), 0, st, (const int32_t*)A->rowptr,
-                           (const int32_t*)A->col, A->val, (const int32_t*)A->orig, n, d_tarl, tarl_dim, (const uint8_t*)notarl.p, d_dino, dino_dim,
-                           alpha, theta, gamma);
-      else
-        hipLaunchKernelGGL((k_weights_lanes<512, 384, 32>), dim3((unsigned)((n + 31) / 32)), dim3(512), 0, st, (const int32_t*)A->rowptr,
-                           (const int32_t*)A->col, A->val, (const int32_t*)A->orig, n, d_tarl, tarl_dim, (const uint8_t*)notarl.p, d_dino, dino_dim,
-                           alpha, theta, gamma);
-    } else {
-    // wave per row (SAM factor, widths that are not multiples of 16): the row's own features stay in registers
-    // when the width is the reference's (96-d TARL, 384-d DINO);
-    // an absent factor takes the width-0 instantiation so that it costs no registers
-    const bool t96 = d_tarl != nullptr && tarl_dim == 96, d384 = d_dino != nullptr && dino_dim == 384;
-#define AI_LAUNCH_W(TK, DK)                                                                                                          \
-  hipLaunchKernelGGL((k_weights<TK, DK>), dim3(gw), dim3(AI_BLOCK), 0, st, (const int32_t*)A->rowptr, (const int32_t*)A->col, A->val, \
-                     (const int32_t*)A->orig, n, d_tarl, tarl_dim, (const uint8_t*)notarl.p, d_dino, dino_dim, alpha, theta, gamma, d_sam, \
-                     sam_views, beta, 0)
-    if (t96 && d384)
-      AI_LAUNCH_W(6, 24);
-    else if (t96)
-      AI_LAUNCH_W(6, 0);
-    else if (d384)
-      AI_LAUNCH_W(0, 24);
-    else
-      AI_LAUNCH_W(0, 0);
-#undef AI_LAUNCH_W
-    }
-    AI_HIPF(hipGetLastError());
-  }
+  launch_weights(st, A->rowptr, A->col, A->val, A->orig, n, d_tarl, tarl_dim, notarl.p, d_dino, dino_dim, alpha, theta, gamma, d_sam, sam_views,
+                 beta);
+  AI_HIPF(hipGetLastError());
   AI_HIPF(hipStreamSynchronize(st));
   *out = A;
   return AI_OK;
@@ -1013,3 +1047,5 @@ extern "C" int ai_affinity_apply_camera(ai_ctx* ctx, ai_csr* csr, const double* 
   AI_HIP(hipStreamSynchronize(st));
   return AI_OK;
 }
+
+#include "ai_affinity_batch.inc"

@@ -23,10 +23,10 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _ffi
-from ._buffers import HOST, Place, cat_int32, is_device_tensor as _is_device_tensor, offsets_of, place_of
+from ._buffers import HOST, Place, cat_int32, is_device_tensor as _is_device_tensor, offsets_of, place_of, segmented
 from .config import CONFIG, PROXIMITY_THRESHOLD, SPLIT_LIM
 
-__all__ = ["Context", "DeviceGraph", "get_affinity_matrix", "build_affinity", "normalized_cut", "ncuts",
+__all__ = ["Context", "DeviceGraph", "get_affinity_matrix", "build_affinity", "build_affinity_batch", "normalized_cut", "ncuts",
            "ncuts_labels", "ncuts_labels_batch", "ncuts_chunk", "default_context", "last_stats",
            "CutTree", "ncuts_tree", "ncuts_tree_batch", "relabel", "normalized_cut_sweep"]
 
@@ -214,6 +214,67 @@ def build_affinity(points, tarl=None, dino=None, *, alpha=CONFIG["alpha"], theta
                                                         float(beta if es is not None else 0.0), float(gamma if ed is not None else 0.0),
                                                         place.mem), "ai_affinity_apply_camera")
     return graph
+
+
+def _batch_inputs(points, tarl, dino, offsets, theta, gamma):
+    """The checked inputs of `build_affinity_batch`: (place, points, tarl, dino, offsets).  Touches no library."""
+    if gamma and isinstance(dino, (list, tuple)) and offsets is not None:
+        raise ValueError("dino: a list is one matrix per camera, which the batched build does not take (apply the extra cameras per "
+                         "graph); with offsets pass one concatenated matrix")
+    if gamma and (dino is None or (isinstance(dino, (list, tuple)) and not dino)):
+        raise ValueError("The length should be longer than 0!")  # ncuts_utils.py:126-127
+    if theta and tarl is None:
+        raise ValueError("theta != 0 needs TARL features")
+    first = points if offsets is not None else next(iter(points), None)
+    place = place_of(first)
+    used = [(f, nm) for f, w, nm in ((tarl, theta, "tarl"), (dino, gamma, "dino")) if w]
+    for f, _ in [(points, "points")] + used:
+        for a in (f if isinstance(f, (list, tuple)) else [f]):
+            if _is_device_tensor(a) != (place.device is not None):
+                raise ValueError("host arrays and device tensors are mixed: points and features of every chunk live in one place")
+    if offsets is None:
+        if not isinstance(points, (list, tuple)):
+            raise ValueError("points: a list of per-chunk arrays, or one array together with its offsets, is expected")
+        for f, nm in used:
+            if not isinstance(f, (list, tuple)) or len(f) != len(points):
+                raise ValueError(f"{nm}: one matrix per chunk expected, as for points ({len(points)} chunks); a list of cameras is "
+                                 "not taken here")
+    pts, off = segmented(points, offsets, 3, np.float64, "points", place)
+    if off.size < 2 or int(off[0]) != 0 or int(off[-1]) != int(pts.shape[0]):
+        raise ValueError("offsets must start at 0, end at the number of rows and hold at least one chunk")
+    out = []
+    for f, w, nm in ((tarl, theta, "tarl"), (dino, gamma, "dino")):
+        if not w:
+            out.append(None)
+            continue
+        m, foff = segmented(f, offsets, None, np.float64, nm, place)
+        if int(m.shape[0]) != int(pts.shape[0]) or not np.array_equal(foff, off):
+            raise ValueError(f"{nm} has {int(m.shape[0])} rows for {int(pts.shape[0])} points (one feature row per point of every chunk)")
+        out.append(m)
+    return place, pts, out[0], out[1], off
+
+
+def build_affinity_batch(points, tarl=None, dino=None, *, offsets=None, alpha=CONFIG["alpha"], theta=CONFIG["theta"],
+                         gamma=CONFIG["gamma"], radius=PROXIMITY_THRESHOLD, group_rows=None, ctx: Context | None = None):
+    """`build_affinity` for every chunk of a map in ONE device call (``ai_affinity_build_batch``): a list of `DeviceGraph`, each bit
+    for bit the graph `build_affinity` gives for its chunk alone, whichever chunks share the call.
+
+    ``points`` / ``tarl`` / ``dino``: one array per chunk, or the concatenated rows with ``offsets`` (C + 1) -- NumPy arrays, or
+    float64 torch tensors on the context's GPU, used in place (`points_api.tarl_pool_map`'s concatenated output and its
+    ``chunk_offsets`` go straight in).  ``group_rows``: rows of the chunks that are built together (None: the library's 2^21);
+    it bounds the call's workspace and changes no bit.  No SAM factor and one camera: extra cameras are applied per graph."""
+    place, pts, t, d, off = _batch_inputs(points, tarl, dino, offsets, theta, gamma)
+    ctx = ctx or default_context()
+    k = int(off.size) - 1
+    hs = (C.c_void_p * k)()
+    mem = place.mem
+    place.sync()   # the producers of the caller's buffers have finished
+    st = _ffi.load().ai_affinity_build_batch(
+        ctx._h, place.addr(pts), off.ctypes.data, k, place.addr(t), t.shape[1] if t is not None else 0, place.addr(d),
+        d.shape[1] if d is not None else 0, float(alpha or 0.0), float(theta or 0.0), float(gamma or 0.0), float(radius),
+        int(group_rows or 0), mem, hs)
+    _ffi.check(st, "ai_affinity_build_batch")
+    return [DeviceGraph(ctx, C.c_void_p(h)) for h in hs]
 
 
 def get_affinity_matrix(points, tarl=None, dino=None, *, alpha=CONFIG["alpha"], theta=CONFIG["theta"],

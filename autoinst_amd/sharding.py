@@ -126,7 +126,7 @@ def gather_labels(local: dict, device=None, force: bool = False):
 
 
 def run_chunks(chunks, *, threads: int = 2, batch: int = 12, device: int | None = None, alpha=None, theta=None, gamma=None,
-               T=None, split_lim=None, contexts=None, builders: int = 1, tree: bool = False):
+               T=None, split_lim=None, contexts=None, builders: int = 1, tree: bool = False, batched_build: bool = False):
     """The chunk loop of ``run_pipeline.py:160-179`` for the chunks of ONE rank / GPU.
 
     ``chunks``: sequence of ``(points, tarl)`` or ``(points, tarl, dino)`` (host arrays or device tensors; ``tarl`` / ``dino``
@@ -142,6 +142,10 @@ def run_chunks(chunks, *, threads: int = 2, batch: int = 12, device: int | None 
 
     ``tree=True``: ``T`` is the largest threshold of interest (``T_max``) and the result is one `ncuts_api.CutTree` per chunk
     instead of its label array: `ncuts_api.relabel` then gives the labels at any ``T' <= T`` without another cut.
+
+    ``batched_build=True``: the graphs of a batch come out of ONE `ncuts_api.build_affinity_batch` call instead of one
+    `build_affinity` call per chunk (the same graphs bit for bit, so the same labels); a batch whose chunks do not all carry the
+    same features at the same widths, in the same place, is built by the loop.
     """
     import queue
     import threading
@@ -175,7 +179,16 @@ def run_chunks(chunks, *, threads: int = 2, batch: int = 12, device: int | None 
     out = [None] * n_chunks
     errors = []
 
+    def feature_shape(c):   # widths of tarl / dino (None: absent) and whether the chunk lives on the device
+        return tuple(None if len(c) <= k or c[k] is None else int(c[k].shape[1]) for k in (1, 2)) + (bool(getattr(c[0], "is_cuda", False)),)
+
     def build(ids, ctx, graphs):
+        if batched_build and len({feature_shape(chunks[i]) for i in ids}) == 1:
+            has_t, has_d = (w is not None for w in feature_shape(chunks[ids[0]])[:2])
+            if (has_t or not cfg["theta"]) and (has_d or not cfg["gamma"]):   # (else the loop raises the single build's error)
+                graphs.extend(api.build_affinity_batch([chunks[i][0] for i in ids], [chunks[i][1] for i in ids] if has_t else None,
+                                                       [chunks[i][2] for i in ids] if has_d else None, ctx=ctx, **cfg))
+                return
         for i in ids:
             c = chunks[i]
             graphs.append(api.build_affinity(c[0], c[1] if len(c) > 1 else None, c[2] if len(c) > 2 else None, ctx=ctx, **cfg))

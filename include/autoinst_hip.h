@@ -107,6 +107,23 @@ int ai_affinity_apply_camera(ai_ctx* ctx, ai_csr* csr, const double* dino, int32
                              int32_t sam_views, double beta, double gamma, int mem_kind);
 
 /*
+ * ai_affinity_build for every chunk of a map in one call (no reference counterpart: the reference builds chunk by chunk inside
+ * ncuts_chunk).  xyz / tarl / dino hold the rows of all chunks one after the other (host or device by mem_kind), chunk c owning
+ * rows off[c] .. off[c + 1]; off is a host array of n_chunks + 1 offsets from 0.  out[c] is a full graph of its own (own buffers,
+ * own copy of the chunk's points; freed in any order, from any thread, accepted wherever a graph of ai_affinity_build is) and
+ * equals, bit for bit in row pointers, columns, values and row order, what ai_affinity_build returns for that chunk's rows alone
+ * with the same weights -- whichever chunks share the call, in whatever order, at whatever group_rows.
+ * The call works through the chunks in groups of whole chunks of at most group_rows rows (<= 0: 2^21; a larger chunk is a group
+ * of its own), so its workspace is that of one group however large the map.  The limits of ai_affinity_build hold per chunk.
+ * AI_ERR_BAD_ARG: n_chunks <= 0, off[0] != 0, offsets that decrease, an empty chunk, a coordinate that is not finite (the
+ * message names the first offending chunk), theta != 0 without tarl, gamma != 0 without dino.  On any failure every out[c] is
+ * NULL and no graph of the call stays registered.  No SAM factor and no extra cameras here: ai_affinity_apply_camera per graph.
+ */
+int ai_affinity_build_batch(ai_ctx* ctx, const double* xyz, const int64_t* off, int32_t n_chunks, const double* tarl,
+                            int32_t tarl_dim, const double* dino, int32_t dino_dim, double alpha, double theta, double gamma,
+                            double radius, int64_t group_rows, int mem_kind, ai_csr** out);
+
+/*
  * Upload a caller-built symmetric CSR (what ncuts_utils.py:167 hands to
  * normalized_cut at :168).  indptr has n+1 entries.  Row order is kept.
  */
