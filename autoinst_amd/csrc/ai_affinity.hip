@@ -8,11 +8,17 @@
 // point scans its 27 neighbouring cells (count pass, scan, fill pass), and a wave-per-row
 // kernel computes the feature distances only for pairs inside the radius (2*E*F flops
 // instead of 2*N^2*F).
+//
+// Layout of this file: the grid kernels (keys, gather, cell ranges, walk), written once and instantiated for the single build's
+// one grid (OneGrid) and for a group of chunks with a grid each (GroupGrids); the weight kernels; on the host one radius-graph
+// pipeline (RadiusGraph) and launch_weights, which ai_affinity_build* runs on the graph's own buffers and ai_affinity_build_batch
+// (ai_affinity_batch.inc, included at the end) on a group's.  Graphs under construction belong to a GraphOwner (ai_common.h);
+// the host plumbing of a call is ai_entry.h's.
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "ai_common.h"
+#include "ai_entry.h"
 
 namespace {
 
@@ -20,6 +26,15 @@ struct Grid {
   double minx, miny, minz, inv_cell;
   int nx, ny, nz;
 };
+
+struct BGrid {  // the grid of one chunk of a group and where its cells start in the group's cell tables
+  Grid g;
+  int64_t cell0;
+};
+
+#define AI_KEY_BITS 30  // Morton key of a cell: 10 bits per axis (at most 1023 cells on one)
+#define AI_NB_LANES 8   // lanes that walk one row's candidates together
+#define AI_NB_STASH 128 // hits of a row the counting walk keeps (ids + distances): filling the CSR is then a copy
 
 __device__ __forceinline__ uint32_t part1by2(uint32_t x) {
   x &= 0x3ffu;
@@ -38,6 +53,54 @@ __device__ __forceinline__ void cell_of(const Grid& g, double x, double y, doubl
   cy = min(max(cy, 0), g.ny - 1);
   cz = min(max(cz, 0), g.nz - 1);
 }
+
+// the chunk of row i: the c with rows[c] <= i < rows[c + 1] (no chunk is empty)
+__device__ __forceinline__ int b_chunk_of(const int32_t* __restrict__ rows, int nc, int32_t i) {
+  int lo = 0, hi = nc - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (rows[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// Where a row's grid comes from.  The grid kernels below are written once and take one of these two by value.
+// OneGrid, the single build: every row is of chunk 0, the grid is a kernel argument, the cells start at 0, the sort key is the
+// Morton key of the cell.
+struct OneGrid {
+  typedef uint32_t Key;
+  Grid g;
+  int key_bits() const { return AI_KEY_BITS; }
+  __device__ __forceinline__ int chunk_of_input(int64_t) const { return 0; }
+  __device__ __forceinline__ void keep_chunk(int64_t, int) const {}
+  __device__ __forceinline__ int chunk_at(int64_t) const { return 0; }
+  __device__ __forceinline__ Grid grid(int) const { return g; }
+  __device__ __forceinline__ Key key(int, uint32_t morton) const { return morton; }
+  __device__ __forceinline__ void walk_grid(int64_t, int& nx, int& ny, int& nz, int64_t& cell0) const {
+    nx = g.nx, ny = g.ny, nz = g.nz, cell0 = 0;
+  }
+};
+// GroupGrids, a group of the batched build: row i of the input is of the chunk whose range of `rows` holds it, which is also the
+// chunk of POSITION i after the sort (a chunk's rows stay inside its range) and is kept per row in `rchunk`; every chunk has
+// its own grid, its cells start at cell0 of the group's concatenated cell tables, and the sort key is (chunk, Morton key).
+struct GroupGrids {
+  typedef uint64_t Key;
+  const int32_t* rows;
+  int nc;
+  const BGrid* grids;
+  int32_t* rchunk;
+  int key_bits() const { return AI_KEY_BITS + bits_for(nc); }
+  __device__ __forceinline__ int chunk_of_input(int64_t i) const { return b_chunk_of(rows, nc, (int32_t)i); }
+  __device__ __forceinline__ void keep_chunk(int64_t i, int c) const { rchunk[i] = c; }
+  __device__ __forceinline__ int chunk_at(int64_t p) const { return rchunk[p]; }
+  __device__ __forceinline__ Grid grid(int c) const { return grids[c].g; }
+  __device__ __forceinline__ Key key(int c, uint32_t morton) const { return ((uint64_t)c << AI_KEY_BITS) | (uint64_t)morton; }
+  // loaded ONCE per row, before the walk, so that no candidate waits for the grid table
+  __device__ __forceinline__ void walk_grid(int64_t p, int& nx, int& ny, int& nz, int64_t& cell0) const {
+    const BGrid* b = grids + rchunk[p];
+    nx = b->g.nx, ny = b->g.ny, nz = b->g.nz, cell0 = b->cell0;
+  }
+};
 
 // per-block min / max of the coordinates -> part[block][6]
 __global__ __launch_bounds__(AI_BLOCK) void k_bounds(const double* __restrict__ xyz, int64_t n, double* __restrict__ part) {
@@ -75,19 +138,25 @@ __global__ __launch_bounds__(AI_BLOCK) void k_bounds(const double* __restrict__ 
   }
 }
 
-__global__ __launch_bounds__(AI_BLOCK) void k_cell_keys(const double* __restrict__ xyz, int64_t n, Grid g,
-                                                        uint32_t* __restrict__ key, int32_t* __restrict__ idx) {
+// sort key of every input row (and, for a group, the row's chunk)
+template <class SRC>
+__global__ __launch_bounds__(AI_BLOCK) void k_cell_keys(const double* __restrict__ xyz, int64_t n, SRC src,
+                                                        typename SRC::Key* __restrict__ key, int32_t* __restrict__ idx) {
   const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
   if (i >= n) return;
+  const int c = src.chunk_of_input(i);
+  const Grid g = src.grid(c);
   int cx, cy, cz;
   cell_of(g, xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2], cx, cy, cz);
-  key[i] = part1by2((uint32_t)cx) | (part1by2((uint32_t)cy) << 1) | (part1by2((uint32_t)cz) << 2);
+  key[i] = src.key(c, part1by2((uint32_t)cx) | (part1by2((uint32_t)cy) << 1) | (part1by2((uint32_t)cz) << 2));
   idx[i] = (int32_t)i;
+  src.keep_chunk(i, c);
 }
 
-// sorted SoA coordinates + linear cell id per sorted point
+// sorted SoA coordinates + linear cell id (in the grid of the row's chunk) per sorted point
+template <class SRC>
 __global__ __launch_bounds__(AI_BLOCK) void k_gather_sorted(const double* __restrict__ xyz, const int32_t* __restrict__ orig,
-                                                            int64_t n, Grid g, double* __restrict__ X, double* __restrict__ Y,
+                                                            int64_t n, SRC src, double* __restrict__ X, double* __restrict__ Y,
                                                             double* __restrict__ Z, int32_t* __restrict__ cellid) {
   const int64_t p = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
   if (p >= n) return;
@@ -96,18 +165,34 @@ __global__ __launch_bounds__(AI_BLOCK) void k_gather_sorted(const double* __rest
   X[p] = x;
   Y[p] = y;
   Z[p] = z;
+  const Grid g = src.grid(src.chunk_at(p));
   int cx, cy, cz;
   cell_of(g, x, y, z, cx, cy, cz);
   cellid[p] = (cz * g.ny + cy) * g.nx + cx;
 }
 
-__global__ __launch_bounds__(AI_BLOCK) void k_cell_ranges(const int32_t* __restrict__ cellid, int64_t n,
-                                                          int32_t* __restrict__ cstart, int32_t* __restrict__ cend) {
+// Ranges of the sorted points per cell: a range starts where the chunk or the cell changes; chunk ch's cells start at cell0 of
+// the tables.  One body and two kernels with an argument list of their own each: a policy object among the arguments of the
+// single build's kernel changes its kernel-argument segment.
+template <bool GROUP>
+__device__ __forceinline__ void cell_ranges(const int32_t* __restrict__ cellid, const int32_t* __restrict__ rchunk, int64_t n,
+                                            const BGrid* __restrict__ grids, int32_t* __restrict__ cstart,
+                                            int32_t* __restrict__ cend) {
   const int64_t p = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
   if (p >= n) return;
-  const int32_t c = cellid[p];
-  if (p == 0 || cellid[p - 1] != c) cstart[c] = (int32_t)p;
-  if (p == n - 1 || cellid[p + 1] != c) cend[c] = (int32_t)(p + 1);
+  const int32_t c = cellid[p], ch = GROUP ? rchunk[p] : 0;
+  const int64_t cell0 = GROUP ? grids[ch].cell0 : 0;
+  if (p == 0 || (GROUP && rchunk[p - 1] != ch) || cellid[p - 1] != c) cstart[cell0 + c] = (int32_t)p;
+  if (p == n - 1 || (GROUP && rchunk[p + 1] != ch) || cellid[p + 1] != c) cend[cell0 + c] = (int32_t)(p + 1);
+}
+__global__ __launch_bounds__(AI_BLOCK) void k_cell_ranges(const int32_t* __restrict__ cellid, int64_t n,
+                                                          int32_t* __restrict__ cstart, int32_t* __restrict__ cend) {
+  cell_ranges<false>(cellid, nullptr, n, nullptr, cstart, cend);
+}
+__global__ __launch_bounds__(AI_BLOCK) void k_b_cell_ranges(const int32_t* __restrict__ cellid, const int32_t* __restrict__ rchunk, int64_t n,
+                                                            const BGrid* __restrict__ grids, int32_t* __restrict__ cstart,
+                                                            int32_t* __restrict__ cend) {
+  cell_ranges<true>(cellid, rchunk, n, grids, cstart, cend);
 }
 
 // cdist's euclidean kernel: sqrt((dx*dx + dy*dy) + dz*dz), every product and sum rounded on
@@ -128,7 +213,6 @@ __device__ __forceinline__ double dist3(double ax, double ay, double az, double 
 // candidate order with a ballot, so a row's entries keep the order cell by cell, point by point.  FILL = false counts
 // the neighbours within the radius; FILL = true writes their ids and distances.  (One thread per point walking the ~115
 // candidates serially took 0.16 + 0.24 ms per 200k-point chunk.)
-#define AI_NB_LANES 8
 // the walk of one row: `c` is the row's linear cell in a grid of nx * ny * nz cells whose ranges are cstart / cend; returns the
 // number of neighbours.  The single build passes its one grid, the batched build the grid of the row's chunk (its cell tables
 // offset to that chunk's cells), so both visit a row's candidates in the same order.
@@ -195,11 +279,11 @@ __device__ __forceinline__ int32_t nb_walk(const double* __restrict__ X, const d
   return k;
 }
 
-template <bool FILL>
+template <bool FILL, class SRC>
 __global__ __launch_bounds__(AI_BLOCK) void k_neighbours(const double* __restrict__ X, const double* __restrict__ Y,
                                                          const double* __restrict__ Z, const int32_t* __restrict__ cellid,
                                                          const int32_t* __restrict__ cstart, const int32_t* __restrict__ cend,
-                                                         int64_t n, Grid g, double radius, int32_t* __restrict__ cnt,
+                                                         int64_t n, SRC src, double radius, int32_t* __restrict__ cnt,
                                                          const int32_t* __restrict__ rowptr, int32_t* __restrict__ col,
                                                          double* __restrict__ dist, int32_t* __restrict__ stash_col,
                                                          double* __restrict__ stash_dist, int stash_cap,
@@ -216,8 +300,11 @@ __global__ __launch_bounds__(AI_BLOCK) void k_neighbours(const double* __restric
   const int64_t pp = live ? p : n - 1;
   const double x = X[pp], y = Y[pp], z = Z[pp];
   const int32_t c = cellid[pp];
+  int nx, ny, nz;
+  int64_t cell0;
+  src.walk_grid(pp, nx, ny, nz, cell0);
   const int32_t base = (FILL && live) ? rowptr[p] : 0;
-  const int32_t k = nb_walk<FILL>(X, Y, Z, cstart, cend, g.nx, g.ny, g.nz, live, p, l, sub, x, y, z, c, radius, base, col, dist,
+  const int32_t k = nb_walk<FILL>(X, Y, Z, cstart + cell0, cend + cell0, nx, ny, nz, live, p, l, sub, x, y, z, c, radius, base, col, dist,
                                   stash_col, stash_dist, stash_cap);
   if (!FILL && live && l == 0) cnt[p] = k;
 }
@@ -460,10 +547,11 @@ __device__ unsigned long long g_aw_phase[8];
 #define AW_STAMP(k) do { } while (0)
 #endif
 #define AW_ECAP 2048   // entries of a 16-row tile whose hash slot is remembered (more: fallback); twice that for 32 rows
-// NT = threads per block = 16 x the rows of a tile.  256: 16-row tiles, ~200 distinct columns, 32 KB slabs, three blocks per CU.
-// 512 (round 5): 32-row tiles -- consecutive Morton rows share their neighbour cells, so 32 rows touch ~300 distinct columns, not
-// 2 x 200: a quarter fewer staged bytes per row, and the staging wait is what the kernel's time is -- 48 KB slabs,
-// two blocks per CU (the same 96 KB of slabs in flight per CU), 128 registers per lane instead of 168.
+// NT = threads per block = 16 x the rows of a tile.  256, the default: 16-row tiles, ~200 distinct columns, 32 KB slabs, three
+// blocks per CU.  512 (AI_WEIGHTS_TILE=32) is kept for re-measurement and is not what ships: 32-row tiles -- consecutive Morton rows
+// share their neighbour cells, so 32 rows touch ~300 distinct columns, not 2 x 200: a quarter fewer staged bytes per row -- 48 KB
+// slabs, two blocks per CU (the same 96 KB of slabs in flight per CU), 128 registers per lane instead of 168.  Same bits in both
+// (tests/test_gpu_affinity.py).
 template <int NT, int AW_MAXD, int ACC>
 __global__ __launch_bounds__(NT, (NT == 256 ? 3 : 4)) void k_weights_lanes(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                                double* __restrict__ val, const int32_t* __restrict__ orig, int64_t n,
@@ -701,20 +789,26 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 3 : 4)) void k_weights_lanes(const
 }  // namespace
 
 // ----------------------------------------------------------------------------- host side
-static int upload_if_host(const double* src, size_t count, int mem_kind, DevBuf<double>& own, const double** dev,
-                          hipStream_t stream) {
-  if (src == nullptr) {
-    *dev = nullptr;
-    return AI_OK;
-  }
-  if (mem_kind == AI_MEM_DEVICE) {
-    *dev = src;
-    return AI_OK;
-  }
-  AI_TRY(own.alloc(count));
-  AI_HIP(hipMemcpyAsync(own.p, src, count * sizeof(double), hipMemcpyHostToDevice, stream));
-  *dev = own.p;
+#define AI_MAX_ROWS ((int64_t)1 << 30)  // rows of one graph, and of one group: row ids and positions are int32
+
+// what both build entries ask of their weights and features
+static int check_features(const char* entry, double gamma, const double* dino, int32_t dino_dim, double theta, const double* tarl,
+                          int32_t tarl_dim) {
+  // ncuts_utils.py:126-127 raises ValueError("The length should be longer than 0!")
+  if (gamma != 0.0 && (dino == nullptr || dino_dim <= 0))
+    return bad_arg(entry, "gamma != 0 needs DINO features (the reference raises ValueError here)");
+  if (theta != 0.0 && (tarl == nullptr || tarl_dim <= 0)) return bad_arg(entry, "theta != 0 needs TARL features");
   return AI_OK;
+}
+
+// per-block bounds records (the first six values of each: min xyz, max xyz) folded into one box
+static void fold_bounds(const double* part, int nblocks, int stride, double mn[3], double mx[3]) {
+  for (int a = 0; a < 3; ++a) mn[a] = 1e300, mx[a] = -1e300;
+  for (int b = 0; b < nblocks; ++b)
+    for (int a = 0; a < 3; ++a) {
+      if (part[b * stride + a] < mn[a]) mn[a] = part[b * stride + a];
+      if (part[b * stride + 3 + a] > mx[a]) mx[a] = part[b * stride + 3 + a];
+    }
 }
 
 // The cell grid of one cloud from its bounding box (cell = radius, a hair wider).  0: fine; 1: the box is not finite; 2: more than
@@ -738,10 +832,17 @@ static int affinity_grid(const double mn[3], const double mx[3], double radius, 
 }
 
 // The feature factors of a graph whose val[] holds the spatial distances: the launch of the single build, which the batched build
-// makes on the rows of a whole group (a stored value does not depend on the tile it is computed in).
-static void launch_weights(hipStream_t st, int32_t* rowptr, int32_t* col, double* val, int32_t* orig, int64_t n, const double* d_tarl,
-                           int32_t tarl_dim, uint8_t* notarl, const double* d_dino, int32_t dino_dim, double alpha, double theta,
-                           double gamma, const int32_t* d_sam, int32_t sam_views, double beta) {
+// makes on the rows of a whole group (a stored value does not depend on the tile it is computed in).  With TARL features the
+// rows without one are flagged first (k_zero_rows).
+static int launch_weights(hipStream_t st, int32_t* rowptr, int32_t* col, double* val, int32_t* orig, int64_t n, const double* d_tarl,
+                          int32_t tarl_dim, const double* d_dino, int32_t dino_dim, double alpha, double theta, double gamma,
+                          const int32_t* d_sam, int32_t sam_views, double beta, DevBuf<uint8_t>& flags) {
+  if (d_tarl) {
+    AI_TRY(flags.alloc(n));
+    hipLaunchKernelGGL(k_zero_rows, dim3(grid_for(n * 16)), dim3(AI_BLOCK), 0, st, d_tarl, tarl_dim, (const int32_t*)orig, n, flags.p);
+    AI_KERNEL_CHECK();
+  }
+  uint8_t* const notarl = flags.p;
   const unsigned gw = (unsigned)((n + (AI_BLOCK / 64) - 1) / (AI_BLOCK / 64));
   const bool has_t = d_tarl != nullptr, has_d = d_dino != nullptr;
   static const int force_rowwise = getenv("AI_WEIGHTS_ROWWISE") ? atoi(getenv("AI_WEIGHTS_ROWWISE")) : 0;
@@ -780,6 +881,8 @@ static void launch_weights(hipStream_t st, int32_t* rowptr, int32_t* col, double
       AI_LAUNCH_W(0, 0);
 #undef AI_LAUNCH_W
   }
+  AI_KERNEL_CHECK();
+  return AI_OK;
 }
 
 #ifdef AW_PHASES
@@ -793,6 +896,110 @@ extern "C" int ai_debug_aw_phases(unsigned long long* out, int reset) {
 }
 #endif
 
+// The radius graph of n rows whose grids come from `src` (OneGrid: the single build; GroupGrids: a group of the batched build), in
+// the two phases its memory asks for: count() leaves the rows' entry counts scanned into the caller's `rowptr` and the sort's
+// permutation in the caller's `orig`; the caller queues what it wants to read back with the totals, calls totals(), judges them
+// and allocates col / val; fill() writes the columns and the spatial distances.  The object owns the workspace between the phases.
+// A graph with 2^31 entries or more is refused (the row pointers are int32: the scan has wrapped, the 64-bit total has not), and
+// one with fewer entries than rows is broken (every point is its own neighbour).
+inline bool nnz_overflows(unsigned long long nnz) { return nnz >= (1ull << 31); }
+inline bool nnz_below_rows(int64_t nnz, int64_t rows) { return nnz < rows; }
+
+// the one grid kernel with two argument lists (see cell_ranges)
+static void launch_cell_ranges(const OneGrid&, hipStream_t st, unsigned gb, const int32_t* cellid, int64_t n, int32_t* cstart, int32_t* cend) {
+  hipLaunchKernelGGL(k_cell_ranges, dim3(gb), dim3(AI_BLOCK), 0, st, cellid, n, cstart, cend);
+}
+static void launch_cell_ranges(const GroupGrids& s, hipStream_t st, unsigned gb, const int32_t* cellid, int64_t n, int32_t* cstart,
+                               int32_t* cend) {
+  hipLaunchKernelGGL(k_b_cell_ranges, dim3(gb), dim3(AI_BLOCK), 0, st, cellid, (const int32_t*)s.rchunk, n, s.grids, cstart, cend);
+}
+
+template <class SRC>
+struct RadiusGraph {
+  hipStream_t st;
+  SRC src;
+  int64_t n, ncell;
+  double radius;
+  DevBuf<typename SRC::Key> key, key2;
+  DevBuf<int32_t> idx, cellid, cstart, cend, cnt, scantmp, stash_col;
+  DevBuf<double> X, Y, Z, stash_dist;
+  DevBuf<unsigned long long> total;
+  unsigned long long tot2[2] = {0, 0};
+  unsigned long long nnz = 0, rows_over = 0;  // after totals(): entries, rows with more than AI_NB_STASH of them
+
+  RadiusGraph(hipStream_t st_, const SRC& src_, int64_t n_, int64_t ncell_, double radius_)
+      : st(st_), src(src_), n(n_), ncell(ncell_), radius(radius_) {}
+
+  int count(const double* d_xyz, int32_t* orig, int32_t* rowptr) {
+    const unsigned gb = grid_for(n), gnb = grid_for(n * AI_NB_LANES);
+    AI_TRY(key.alloc(n));
+    AI_TRY(key2.alloc(n));
+    AI_TRY(idx.alloc(n));
+    hipLaunchKernelGGL(k_cell_keys<SRC>, dim3(gb), dim3(AI_BLOCK), 0, st, d_xyz, n, src, key.p, idx.p);
+    AI_KERNEL_CHECK();
+    {
+      size_t tmp_bytes = 0;
+      AI_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key.p, key2.p, idx.p, orig, (size_t)n, 0, src.key_bits(), st));
+      DevBuf<uint8_t> tmp;
+      AI_TRY(tmp.alloc(tmp_bytes));
+      AI_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, key.p, key2.p, idx.p, orig, (size_t)n, 0, src.key_bits(), st));
+      // tmp comes from the call's arena (released when the call returns, after the final synchronisation): no wait here
+      if (!ai_current_arena()) AI_HIP(hipStreamSynchronize(st));
+    }
+    AI_TRY(X.alloc(n));
+    AI_TRY(Y.alloc(n));
+    AI_TRY(Z.alloc(n));
+    AI_TRY(cellid.alloc(n));
+    AI_TRY(cstart.alloc(ncell));
+    AI_TRY(cend.alloc(ncell));
+    AI_TRY(cnt.alloc(n + 1));
+    AI_TRY(scantmp.alloc(ai_scan_tmp_elems(n)));
+    AI_TRY(stash_col.alloc((size_t)n * AI_NB_STASH));
+    AI_TRY(stash_dist.alloc((size_t)n * AI_NB_STASH));
+    AI_TRY(total.alloc(2));
+    hipLaunchKernelGGL(k_gather_sorted<SRC>, dim3(gb), dim3(AI_BLOCK), 0, st, d_xyz, (const int32_t*)orig, n, src, X.p, Y.p, Z.p, cellid.p);
+    AI_KERNEL_CHECK();
+    AI_HIP(hipMemsetAsync(cstart.p, 0xff, (size_t)ncell * sizeof(int32_t), st));
+    AI_HIP(hipMemsetAsync(cend.p, 0, (size_t)ncell * sizeof(int32_t), st));
+    launch_cell_ranges(src, st, gb, cellid.p, n, cstart.p, cend.p);
+    AI_KERNEL_CHECK();
+    // the counting walk keeps its hits (up to AI_NB_STASH per row)
+    hipLaunchKernelGGL((k_neighbours<false, SRC>), dim3(gnb), dim3(AI_BLOCK), 0, st, X.p, Y.p, Z.p, cellid.p, cstart.p, cend.p, n, src, radius,
+                       cnt.p, (const int32_t*)nullptr, (int32_t*)nullptr, (double*)nullptr, stash_col.p, stash_dist.p, AI_NB_STASH,
+                       (const int32_t*)nullptr);
+    AI_KERNEL_CHECK();
+    AI_HIP(hipMemsetAsync(total.p, 0, 2 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_count_total, dim3(256), dim3(AI_BLOCK), 0, st, (const int32_t*)cnt.p, n, total.p);
+    AI_KERNEL_CHECK();
+    hipLaunchKernelGGL(k_count_over, dim3(256), dim3(AI_BLOCK), 0, st, (const int32_t*)cnt.p, n, AI_NB_STASH, total.p + 1);
+    AI_KERNEL_CHECK();
+    return ai_exclusive_scan_i32(st, cnt.p, rowptr, n, scantmp.p);
+  }
+
+  // the totals come down after whatever the caller has queued; ONE host synchronisation
+  int totals() {
+    AI_HIP(hipMemcpyAsync(tot2, total.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    AI_HIP(hipStreamSynchronize(st));
+    nnz = tot2[0], rows_over = tot2[1];
+    return AI_OK;
+  }
+
+  int fill(const int32_t* rowptr, int32_t* col, double* val) {
+    const unsigned gnb = grid_for(n * AI_NB_LANES);
+    hipLaunchKernelGGL(k_nb_unstash, dim3(gnb), dim3(AI_BLOCK), 0, st, (const int32_t*)cnt.p, rowptr, (const int32_t*)stash_col.p,
+                       (const double*)stash_dist.p, AI_NB_STASH, n, col, val);
+    AI_KERNEL_CHECK();
+    if (rows_over > 0) {  // dense clouds: the rows that did not fit the stash are walked a second time
+      hipLaunchKernelGGL((k_neighbours<true, SRC>), dim3(gnb), dim3(AI_BLOCK), 0, st, X.p, Y.p, Z.p, cellid.p, cstart.p, cend.p, n, src,
+                         radius, (int32_t*)nullptr, rowptr, col, val, (int32_t*)nullptr, (double*)nullptr, AI_NB_STASH,
+                         (const int32_t*)cnt.p);
+      AI_KERNEL_CHECK();
+    }
+    return AI_OK;
+  }
+
+};
+
 extern "C" int ai_affinity_build(ai_ctx* ctx, const double* xyz, int64_t n, const double* tarl, int32_t tarl_dim,
                                  const double* dino, int32_t dino_dim, double alpha, double theta, double gamma,
                                  double radius, int mem_kind, ai_csr** out) {
@@ -802,51 +1009,33 @@ extern "C" int ai_affinity_build(ai_ctx* ctx, const double* xyz, int64_t n, cons
 extern "C" int ai_affinity_build_sam(ai_ctx* ctx, const double* xyz, int64_t n, const double* tarl, int32_t tarl_dim,
                                      const double* dino, int32_t dino_dim, const int32_t* sam, int32_t sam_views, double alpha,
                                      double beta, double gamma, double theta, double radius, int mem_kind, ai_csr** out) {
-  if (!ctx || !xyz || !out || n <= 0 || !(radius > 0.0)) {
-    ai_set_error("ai_affinity_build: bad argument (ctx/xyz/out null, n <= 0 or radius <= 0)");
-    return AI_ERR_BAD_ARG;
-  }
-  if (beta != 0.0 && (sam == nullptr || sam_views <= 0)) {
-    // ncuts_utils.py:116-117 raises ValueError("The length should be longer than 0!")
-    ai_set_error("ai_affinity_build: beta != 0 needs SAM ids (the reference raises ValueError here)");
-    return AI_ERR_BAD_ARG;
-  }
-  if (n >= (int64_t)1 << 30) {
+  static const char* const entry = "ai_affinity_build";
+  if (!ctx || !xyz || !out || n <= 0 || !(radius > 0.0)) return bad_arg(entry, "bad argument (ctx/xyz/out null, n <= 0 or radius <= 0)");
+  // ncuts_utils.py:116-117 raises ValueError("The length should be longer than 0!")
+  if (beta != 0.0 && (sam == nullptr || sam_views <= 0))
+    return bad_arg(entry, "beta != 0 needs SAM ids (the reference raises ValueError here)");
+  if (n >= AI_MAX_ROWS) {
     ai_set_error("ai_affinity_build: n = %lld exceeds the int32 row-id range of this build", (long long)n);
     return AI_ERR_BAD_ARG;
   }
-  if (gamma != 0.0 && (dino == nullptr || dino_dim <= 0)) {
-    // ncuts_utils.py:126-127 raises ValueError("The length should be longer than 0!")
-    ai_set_error("ai_affinity_build: gamma != 0 needs DINO features (the reference raises ValueError here)");
-    return AI_ERR_BAD_ARG;
-  }
-  if (theta != 0.0 && (tarl == nullptr || tarl_dim <= 0)) {
-    ai_set_error("ai_affinity_build: theta != 0 needs TARL features");
-    return AI_ERR_BAD_ARG;
-  }
+  AI_TRY(check_features(entry, gamma, dino, dino_dim, theta, tarl, tarl_dim));
   AI_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   *out = nullptr;
-  ArenaScope arena_scope(&ctx->arena);  // scratch comes from the context's arena; the graph itself is hipMalloc'd
+  ArenaScope arena_scope(&ctx->arena);  // scratch comes from the context's arena; the graph itself is from its graph cache
 
+  // an absent factor stays a null pointer
   DevBuf<double> own_xyz, own_tarl, own_dino;
-  const double *d_xyz, *d_tarl, *d_dino;
-  AI_TRY(upload_if_host(xyz, (size_t)n * 3, mem_kind, own_xyz, &d_xyz, st));
-  AI_TRY(upload_if_host(theta != 0.0 ? tarl : nullptr, (size_t)n * (size_t)(tarl_dim > 0 ? tarl_dim : 0), mem_kind, own_tarl, &d_tarl, st));
-  AI_TRY(upload_if_host(gamma != 0.0 ? dino : nullptr, (size_t)n * (size_t)(dino_dim > 0 ? dino_dim : 0), mem_kind, own_dino, &d_dino, st));
   DevBuf<int32_t> own_sam;
+  const double *d_xyz = nullptr, *d_tarl = nullptr, *d_dino = nullptr;
   const int32_t* d_sam = nullptr;
-  if (beta != 0.0) {
-    if (mem_kind == AI_MEM_DEVICE) {
-      d_sam = sam;
-    } else {
-      AI_TRY(own_sam.alloc((size_t)n * sam_views));
-      AI_HIP(hipMemcpyAsync(own_sam.p, sam, (size_t)n * sam_views * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      d_sam = own_sam.p;
-    }
-  }
+  AI_TRY(to_device(xyz, (size_t)n * 3, mem_kind, own_xyz, &d_xyz, st));
+  if (theta != 0.0) AI_TRY(to_device(tarl, (size_t)n * (size_t)tarl_dim, mem_kind, own_tarl, &d_tarl, st));
+  if (gamma != 0.0) AI_TRY(to_device(dino, (size_t)n * (size_t)dino_dim, mem_kind, own_dino, &d_dino, st));
+  if (beta != 0.0) AI_TRY(to_device(sam, (size_t)n * sam_views, mem_kind, own_sam, &d_sam, st));
 
-  // bounds
+  // the grid from the bounding box.  (A NaN coordinate is not noticed here -- fmin / fmax pass it by -- where the batched build
+  // refuses it: DESIGN.md section 24.)
   const int nb = 256;
   DevBuf<double> part;
   AI_TRY(part.alloc((size_t)nb * 6));
@@ -855,19 +1044,13 @@ extern "C" int ai_affinity_build_sam(ai_ctx* ctx, const double* xyz, int64_t n, 
   std::vector<double> hpart((size_t)nb * 6);
   AI_HIP(hipMemcpyAsync(hpart.data(), part.p, hpart.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   AI_HIP(hipStreamSynchronize(st));
-  double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
-  for (int b = 0; b < nb; ++b)
-    for (int a = 0; a < 3; ++a) {
-      if (hpart[b * 6 + a] < mn[a]) mn[a] = hpart[b * 6 + a];
-      if (hpart[b * 6 + 3 + a] > mx[a]) mx[a] = hpart[b * 6 + 3 + a];
-    }
-  Grid g;
+  double mn[3], mx[3], ext[3];
+  fold_bounds(hpart.data(), nb, 6, mn, mx);
+  OneGrid src;
   int64_t ncell = 0;
-  double ext[3];
-  switch (affinity_grid(mn, mx, radius, g, ncell, ext)) {
+  switch (affinity_grid(mn, mx, radius, src.g, ncell, ext)) {
     case 1:
-      ai_set_error("ai_affinity_build: coordinates are not finite");
-      return AI_ERR_BAD_ARG;
+      return bad_arg(entry, "coordinates are not finite");
     case 2:
       ai_set_error("ai_affinity_build: extent / radius = (%.0f, %.0f, %.0f) exceeds 1023 cells per axis", ext[0], ext[1], ext[2]);
       return AI_ERR_BAD_ARG;
@@ -878,142 +1061,45 @@ extern "C" int ai_affinity_build_sam(ai_ctx* ctx, const double* xyz, int64_t n, 
       break;
   }
 
-  const unsigned gb = (unsigned)((n + AI_BLOCK - 1) / AI_BLOCK);
-  DevBuf<uint32_t> key, key2;
-  DevBuf<int32_t> idx, cellid, cstart, cend, cnt, scantmp;
-  DevBuf<double> X, Y, Z;
-  DevBuf<uint8_t> notarl;
-  AI_TRY(key.alloc(n));
-  AI_TRY(key2.alloc(n));
-  AI_TRY(idx.alloc(n));
-  hipLaunchKernelGGL(k_cell_keys, dim3(gb), dim3(AI_BLOCK), 0, st, d_xyz, n, g, key.p, idx.p);
-  AI_KERNEL_CHECK();
-
-  // the graph object (rows in Morton-cell order, orig[] maps back)
-  ai_csr* A = new ai_csr();
-  A->n = n;
-  A->nnz = 0;
-  A->rowptr = nullptr;
-  A->col = nullptr;
-  A->val = nullptr;
-  A->orig = nullptr;
-  A->device = ctx->device;
-  ai_register_graph(ctx, A);
-  auto fail = [&](int s) {
-    ai_csr_free(ctx, A);
-    return s;
-  };
-#define AI_TRYF(expr)                \
-  do {                               \
-    int _s = (expr);                 \
-    if (_s != AI_OK) return fail(_s); \
-  } while (0)
-#define AI_HIPF(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess) {                                                               \
-      ai_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-      return fail((_e == hipErrorOutOfMemory) ? AI_ERR_OOM : AI_ERR_HIP);                \
-    }                                                                                     \
-  } while (0)
-
-  AI_HIPF(ctx->graphs.alloc((void**)&A->orig, (size_t)n * sizeof(int32_t)));
-  AI_HIPF(ctx->graphs.alloc((void**)&A->rowptr, (size_t)(n + 1) * sizeof(int32_t)));
+  // the graph (rows in Morton-cell order, orig[] maps back); the pipeline writes straight into its buffers
+  GraphOwner owner(ctx);
+  ai_csr* A = owner.add(n, 0);
+  AI_HIP(owner.alloc(&A->orig, (size_t)n));
+  AI_HIP(owner.alloc(&A->rowptr, (size_t)n + 1));
   // the graph keeps its points (24 bytes per point): the cut's ancestor-less segments start from their principal-axis coordinate
-  AI_HIPF(ctx->graphs.alloc((void**)&A->xyz, (size_t)n * 3 * sizeof(double)));
-  AI_HIPF(hipMemcpyAsync(A->xyz, d_xyz, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
-  {
-    size_t tmp_bytes = 0;
-    AI_HIPF(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key.p, key2.p, idx.p, A->orig, (size_t)n, 0, 30, st));
-    DevBuf<uint8_t> tmp;
-    AI_TRYF(tmp.alloc(tmp_bytes));
-    AI_HIPF(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, key.p, key2.p, idx.p, A->orig, (size_t)n, 0, 30, st));
-    // tmp comes from the call's arena (released when the call returns, after the final synchronisation): no wait here
-    if (!ai_current_arena()) AI_HIPF(hipStreamSynchronize(st));
-  }
-  AI_TRYF(X.alloc(n));
-  AI_TRYF(Y.alloc(n));
-  AI_TRYF(Z.alloc(n));
-  AI_TRYF(cellid.alloc(n));
-  AI_TRYF(cstart.alloc(ncell));
-  AI_TRYF(cend.alloc(ncell));
-  AI_TRYF(cnt.alloc(n + 1));
-  AI_TRYF(scantmp.alloc(ai_scan_tmp_elems(n)));
-  hipLaunchKernelGGL(k_gather_sorted, dim3(gb), dim3(AI_BLOCK), 0, st, d_xyz, A->orig, n, g, X.p, Y.p, Z.p, cellid.p);
-  AI_HIPF(hipGetLastError());
-  AI_HIPF(hipMemsetAsync(cstart.p, 0xff, (size_t)ncell * sizeof(int32_t), st));
-  AI_HIPF(hipMemsetAsync(cend.p, 0, (size_t)ncell * sizeof(int32_t), st));
-  hipLaunchKernelGGL(k_cell_ranges, dim3(gb), dim3(AI_BLOCK), 0, st, cellid.p, n, cstart.p, cend.p);
-  AI_HIPF(hipGetLastError());
-  const unsigned gnb = (unsigned)((n * AI_NB_LANES + AI_BLOCK - 1) / AI_BLOCK);
-  // the counting walk keeps its hits (up to AI_NB_STASH per row), so that filling the CSR is a copy
-  constexpr int AI_NB_STASH = 128;
-  DevBuf<int32_t> stash_col;
-  DevBuf<double> stash_dist;
-  AI_TRYF(stash_col.alloc((size_t)n * AI_NB_STASH));
-  AI_TRYF(stash_dist.alloc((size_t)n * AI_NB_STASH));
-  hipLaunchKernelGGL(k_neighbours<false>, dim3(gnb), dim3(AI_BLOCK), 0, st, X.p, Y.p, Z.p, cellid.p, cstart.p, cend.p, n, g,
-                     radius, cnt.p, (const int32_t*)nullptr, (int32_t*)nullptr, (double*)nullptr, stash_col.p, stash_dist.p, AI_NB_STASH,
-                     (const int32_t*)nullptr);
-  AI_HIPF(hipGetLastError());
-  DevBuf<unsigned long long> total;
-  AI_TRYF(total.alloc(2));
-  AI_HIPF(hipMemsetAsync(total.p, 0, 2 * sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(k_count_total, dim3(256), dim3(AI_BLOCK), 0, st, (const int32_t*)cnt.p, n, total.p);
-  AI_HIPF(hipGetLastError());
-  hipLaunchKernelGGL(k_count_over, dim3(256), dim3(AI_BLOCK), 0, st, (const int32_t*)cnt.p, n, AI_NB_STASH, total.p + 1);
-  AI_HIPF(hipGetLastError());
-  AI_TRYF(ai_exclusive_scan_i32(st, cnt.p, A->rowptr, n, scantmp.p));
+  AI_HIP(owner.alloc(&A->xyz, (size_t)n * 3));
+  AI_HIP(hipMemcpyAsync(A->xyz, d_xyz, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+  RadiusGraph<OneGrid> R(st, src, n, ncell, radius);
+  AI_TRY(R.count(d_xyz, A->orig, A->rowptr));
   int32_t nnz32 = 0;
-  unsigned long long tot2[2] = {0, 0};
-  AI_HIPF(hipMemcpyAsync(&nnz32, A->rowptr + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  AI_HIPF(hipMemcpyAsync(tot2, total.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  AI_HIPF(hipStreamSynchronize(st));
-  const unsigned long long nnz64 = tot2[0], rows_over = tot2[1];
-  if (nnz64 >= (1ull << 31)) {
-    ai_set_error("ai_affinity_build: the radius graph has %llu entries; this build indexes entries with int32 (< 2^31)", nnz64);
-    return fail(AI_ERR_BAD_ARG);
+  AI_HIP(hipMemcpyAsync(&nnz32, A->rowptr + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  AI_TRY(R.totals());
+  if (nnz_overflows(R.nnz)) {
+    ai_set_error("ai_affinity_build: the radius graph has %llu entries; this build indexes entries with int32 (< 2^31)", R.nnz);
+    return AI_ERR_BAD_ARG;
   }
-  if (nnz32 < n) {
+  if (nnz_below_rows(nnz32, n)) {
     ai_set_error("ai_affinity_build: internal error, nnz = %d < n (every point is its own neighbour)", nnz32);
-    return fail(AI_ERR_INTERNAL);
+    return AI_ERR_INTERNAL;
   }
   A->nnz = nnz32;
-  AI_HIPF(ctx->graphs.alloc((void**)&A->col, (size_t)A->nnz * sizeof(int32_t)));
-  AI_HIPF(ctx->graphs.alloc((void**)&A->val, (size_t)A->nnz * sizeof(double)));
-  hipLaunchKernelGGL(k_nb_unstash, dim3(gnb), dim3(AI_BLOCK), 0, st, (const int32_t*)cnt.p, (const int32_t*)A->rowptr, (const int32_t*)stash_col.p,
-                     (const double*)stash_dist.p, AI_NB_STASH, n, A->col, A->val);
-  AI_HIPF(hipGetLastError());
-  if (rows_over > 0) {  // dense clouds: the rows that did not fit the stash are walked a second time
-    hipLaunchKernelGGL(k_neighbours<true>, dim3(gnb), dim3(AI_BLOCK), 0, st, X.p, Y.p, Z.p, cellid.p, cstart.p, cend.p, n, g,
-                       radius, (int32_t*)nullptr, (const int32_t*)A->rowptr, A->col, A->val, (int32_t*)nullptr, (double*)nullptr,
-                       AI_NB_STASH, (const int32_t*)cnt.p);
-    AI_HIPF(hipGetLastError());
-  }
-  if (d_tarl) {
-    AI_TRYF(notarl.alloc(n));
-    const unsigned gz = (unsigned)((n * 16 + AI_BLOCK - 1) / AI_BLOCK);
-    hipLaunchKernelGGL(k_zero_rows, dim3(gz), dim3(AI_BLOCK), 0, st, d_tarl, tarl_dim, A->orig, n, notarl.p);
-    AI_HIPF(hipGetLastError());
-  }
-  launch_weights(st, A->rowptr, A->col, A->val, A->orig, n, d_tarl, tarl_dim, notarl.p, d_dino, dino_dim, alpha, theta, gamma, d_sam, sam_views,
-                 beta);
-  AI_HIPF(hipGetLastError());
-  AI_HIPF(hipStreamSynchronize(st));
-  *out = A;
+  AI_HIP(owner.alloc(&A->col, (size_t)A->nnz));
+  AI_HIP(owner.alloc(&A->val, (size_t)A->nnz));
+  AI_TRY(R.fill(A->rowptr, A->col, A->val));
+  DevBuf<uint8_t> notarl;
+  AI_TRY(launch_weights(st, A->rowptr, A->col, A->val, A->orig, n, d_tarl, tarl_dim, d_dino, dino_dim, alpha, theta, gamma, d_sam, sam_views,
+                        beta, notarl));
+  AI_HIP(hipStreamSynchronize(st));
+  owner.keep(out);
   return AI_OK;
-#undef AI_TRYF
-#undef AI_HIPF
 }
 
 // One more camera's factors on an existing graph (ncuts_utils.py:118-123 and :128-133 loop over the cameras):
 // every stored value is multiplied by exp(-beta * sam fraction) * exp(-gamma * ||dino_i - dino_j||).
 extern "C" int ai_affinity_apply_camera(ai_ctx* ctx, ai_csr* csr, const double* dino, int32_t dino_dim, const int32_t* sam,
                                         int32_t sam_views, double beta, double gamma, int mem_kind) {
-  if (!ctx || !csr || (gamma != 0.0 && (!dino || dino_dim <= 0)) || (beta != 0.0 && (!sam || sam_views <= 0))) {
-    ai_set_error("ai_affinity_apply_camera: bad argument (a non-zero weight needs its feature matrix)");
-    return AI_ERR_BAD_ARG;
-  }
+  if (!ctx || !csr || (gamma != 0.0 && (!dino || dino_dim <= 0)) || (beta != 0.0 && (!sam || sam_views <= 0)))
+    return bad_arg("ai_affinity_apply_camera", "bad argument (a non-zero weight needs its feature matrix)");
   if (gamma == 0.0 && beta == 0.0) return AI_OK;
   AI_CHECK_GRAPH(csr, "ai_affinity_apply_camera");
   AI_HIP(hipSetDevice(ctx->device));
@@ -1024,16 +1110,8 @@ extern "C" int ai_affinity_apply_camera(ai_ctx* ctx, ai_csr* csr, const double* 
   DevBuf<int32_t> own_sam;
   const double* d_dino = nullptr;
   const int32_t* d_sam = nullptr;
-  AI_TRY(upload_if_host(gamma != 0.0 ? dino : nullptr, (size_t)n * (size_t)(dino_dim > 0 ? dino_dim : 0), mem_kind, own_dino, &d_dino, st));
-  if (beta != 0.0) {
-    if (mem_kind == AI_MEM_DEVICE) {
-      d_sam = sam;
-    } else {
-      AI_TRY(own_sam.alloc((size_t)n * sam_views));
-      AI_HIP(hipMemcpyAsync(own_sam.p, sam, (size_t)n * sam_views * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      d_sam = own_sam.p;
-    }
-  }
+  if (gamma != 0.0) AI_TRY(to_device(dino, (size_t)n * (size_t)dino_dim, mem_kind, own_dino, &d_dino, st));
+  if (beta != 0.0) AI_TRY(to_device(sam, (size_t)n * sam_views, mem_kind, own_sam, &d_sam, st));
   const unsigned gw = (unsigned)((n + (AI_BLOCK / 64) - 1) / (AI_BLOCK / 64));
   if (d_dino && dino_dim == 384)
     hipLaunchKernelGGL((k_weights<0, 24>), dim3(gw), dim3(AI_BLOCK), 0, st, (const int32_t*)csr->rowptr, (const int32_t*)csr->col, csr->val,

@@ -395,34 +395,23 @@ extern "C" int ai_csr_from_host(ai_ctx* ctx, int64_t n, const int64_t* indptr, c
       return AI_ERR_BAD_ARG;
     }
   AI_HIP(hipSetDevice(ctx->device));
-  ai_csr* A = new ai_csr();
-  A->n = n;
-  A->nnz = nnz;
-  A->rowptr = nullptr;
-  A->col = nullptr;
-  A->val = nullptr;
-  A->orig = nullptr;
-  A->device = ctx->device;
-  ai_register_graph(ctx, A);
-  hipError_t e1 = ctx->graphs.alloc((void**)&A->rowptr, (size_t)(n + 1) * sizeof(int32_t));
-  hipError_t e2 = ctx->graphs.alloc((void**)&A->col, (size_t)(nnz > 0 ? nnz : 1) * sizeof(int32_t));
-  hipError_t e3 = ctx->graphs.alloc((void**)&A->val, (size_t)(nnz > 0 ? nnz : 1) * sizeof(double));
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
-    ai_csr_free(ctx, A);
+  GraphOwner owner(ctx);  // frees the graph on every return but the last
+  ai_csr* A = owner.add(n, nnz);
+  const size_t cap = (size_t)(nnz > 0 ? nnz : 1);
+  if (owner.alloc(&A->rowptr, (size_t)n + 1) != hipSuccess || owner.alloc(&A->col, cap) != hipSuccess ||
+      owner.alloc(&A->val, cap) != hipSuccess) {
     ai_set_error("ai_csr_from_host: device allocation failed");
     return AI_ERR_OOM;
   }
   hipStream_t st = ctx->stream;
-  hipError_t c1 = hipMemcpyAsync(A->rowptr, rp.data(), (size_t)(n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st);
-  hipError_t c2 = nnz ? hipMemcpyAsync(A->col, indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st) : hipSuccess;
-  hipError_t c3 = nnz ? hipMemcpyAsync(A->val, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st) : hipSuccess;
-  hipError_t c4 = hipStreamSynchronize(st);
-  if (c1 != hipSuccess || c2 != hipSuccess || c3 != hipSuccess || c4 != hipSuccess) {
-    ai_csr_free(ctx, A);
+  if (hipMemcpyAsync(A->rowptr, rp.data(), (size_t)(n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess ||
+      (nnz && hipMemcpyAsync(A->col, indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) ||
+      (nnz && hipMemcpyAsync(A->val, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) ||
+      hipStreamSynchronize(st) != hipSuccess) {
     ai_set_error("ai_csr_from_host: copy to device failed");
     return AI_ERR_HIP;
   }
-  *out = A;
+  owner.keep(out);
   return AI_OK;
 }
 

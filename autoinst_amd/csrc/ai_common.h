@@ -167,6 +167,44 @@ struct ai_csr {
                             // (a temporary view, or the owner was destroyed: then the pointers above are null as well)
 };
 
+// The graphs an API call is making.  A graph is registered with the context as soon as it exists, and its buffers come from the
+// context's graph cache.  A call that ends without keep() has failed: the owner waits for the stream (kernels and copies that write the
+// buffers may still be queued) and frees every graph it made.  keep() hands them to the caller and costs nothing.
+struct GraphOwner {
+  ai_ctx* ctx;
+  std::vector<ai_csr*> made;
+  bool kept = false;
+  explicit GraphOwner(ai_ctx* c) : ctx(c) {}
+  GraphOwner(const GraphOwner&) = delete;
+  GraphOwner& operator=(const GraphOwner&) = delete;
+  ~GraphOwner() {
+    if (kept) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    for (ai_csr* A : made) ai_csr_free(ctx, A);
+  }
+  ai_csr* add(int64_t n, int64_t nnz) {  // a registered graph without buffers
+    ai_csr* A = new ai_csr();
+    A->n = n;
+    A->nnz = nnz;
+    A->rowptr = nullptr;
+    A->col = nullptr;
+    A->val = nullptr;
+    A->orig = nullptr;
+    A->device = ctx->device;
+    ai_register_graph(ctx, A);
+    made.push_back(A);
+    return A;
+  }
+  template <typename T>
+  hipError_t alloc(T** field, size_t count) {  // one buffer of a graph of this owner, e.g. alloc(&A->col, nnz)
+    return ctx->graphs.alloc((void**)field, count * sizeof(T));
+  }
+  void keep(ai_csr** out) {  // out[i] = the i-th graph made
+    for (size_t i = 0; i < made.size(); ++i) out[i] = made[i];
+    kept = true;
+  }
+};
+
 // Device buffer of one API call: carved from the context's arena when one is active (then
 // release is a no-op and the memory is reclaimed when the call ends), else hipMalloc / hipFree.
 template <typename T>

@@ -258,7 +258,7 @@ def _error_calls():
     empty = np.array([0, n[0], n[0], sum(n)])
     back = np.array([0, n[0] + n[1], n[0], sum(n)])
     return g, {
-        "nan": (lambda api: api.build_affinity_batch(nan, tarl, dino, **g["kw"]), "chunk 1"),
+        "nan": (lambda api, **more: api.build_affinity_batch(nan, tarl, dino, **g["kw"], **more), "chunk 1"),
         "empty": (lambda api: api.build_affinity_batch(cat(pts), cat(tarl), cat(dino), offsets=empty, **g["kw"]), "chunk 1"),
         "not_monotone": (lambda api: api.build_affinity_batch(cat(pts), cat(tarl), cat(dino), offsets=back, **g["kw"]), "chunk 1"),
         "theta_without_tarl": (lambda api: api.build_affinity_batch(pts, None, dino, **g["kw"]), "TARL"),
@@ -276,4 +276,17 @@ def test_argument_errors_leave_nothing_behind(api, ctx, single, what):
         call(api)
     assert ctx.mem_info()["graphs_live"] == before
     _compare(g, _batched(api, g, host=True), single, f"after {what}")
+    assert ctx.mem_info()["graphs_live"] == before
+
+
+def test_error_in_a_later_group_frees_the_earlier_groups_graphs(api, ctx, single):
+    """``group_rows=1`` makes every chunk a group of its own, so chunk 0's graph has been made and registered by an earlier group
+    when chunk 1 (a NaN coordinate) is refused: the call's graph owner frees it with the call."""
+    g, calls = _error_calls()
+    call, needle = calls["nan"]
+    before = ctx.mem_info()["graphs_live"]
+    with pytest.raises(ValueError, match=needle):
+        call(api, group_rows=1)
+    assert ctx.mem_info()["graphs_live"] == before
+    _compare(g, _batched(api, g, host=True, group_rows=1), single, "after nan in the second group")
     assert ctx.mem_info()["graphs_live"] == before
