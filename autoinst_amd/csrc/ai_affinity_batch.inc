@@ -116,16 +116,18 @@ __global__ __launch_bounds__(AI_BLOCK) void k_b_split_entries(const int32_t* __r
 // ----------------------------------------------------------------------------- host side
 #define AB_DEFAULT_GROUP_ROWS ((int64_t)1 << 21)
 #define AB_SPLIT 1  // (internal status) the group does not fit an int32 counter or the cell-table limit: halve it and redo
+#define AB_MAX_GROUP_CHUNKS 65535  // chunks of one group: k_b_bounds has one grid row (blockIdx.y) per chunk
 
 // The chunks lo .. hi of the call in groups of whole chunks: at most `budget` rows each (a larger chunk is a group of its own),
-// and a group of several chunks stays inside what its int32 position space and the tiled weights' 32-bit staging offsets hold
-// (fewer than 2^30 rows, rows x widest feature < 2^33), so that its weights path is the one every chunk of it takes alone.
+// at most AB_MAX_GROUP_CHUNKS chunks, and a group of several chunks stays inside what its int32 position space and the tiled
+// weights' 32-bit staging offsets hold (fewer than 2^30 rows, rows x widest feature < 2^33), so that its weights path is the one
+// every chunk of it takes alone.
 static std::vector<int32_t> affinity_groups(const int64_t* off, int32_t n_chunks, int64_t budget, int64_t widest) {
   std::vector<int32_t> cut(1, 0);
   const int64_t cap = std::min(AI_MAX_ROWS, widest > 0 ? (((int64_t)1 << 33) + widest - 1) / widest : AI_MAX_ROWS);
   const int64_t lim = std::min(budget, cap - 1);
   for (int32_t c = 0; c < n_chunks; ++c)
-    if (c > cut.back() && off[c + 1] - off[cut.back()] > lim) cut.push_back(c);
+    if (c > cut.back() && (off[c + 1] - off[cut.back()] > lim || c - cut.back() >= AB_MAX_GROUP_CHUNKS)) cut.push_back(c);
   cut.push_back(n_chunks);
   return cut;
 }
