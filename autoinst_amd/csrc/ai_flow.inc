@@ -1472,8 +1472,13 @@ class Flow {
         AI_KERNEL_CHECK();
       }
       hipLaunchKernelGGL(fk_lz_init, dim3(ncC), dim3(AI_BLOCK), 0, sw, (const Task*)coarseC.p, (const SegRec*)wrecC.p, G, (const double*)u1.p, slabs[0],
-                         pB0.p, cactive.p, gate, w_nbin, warm ? (const double*)warmv.p : (const double*)nullptr);
+                         pB0.p, cactive.p, gate, w_nbin, warm ? (const double*)warmv.p : (const double*)nullptr, pB1.p);
       AI_KERNEL_CHECK();
+      if (warm) {  // starts that carry a warm vector: u1 taken out where the start is all but parallel to it; their partials pB1 -> pB0
+        hipLaunchKernelGGL(fk_lz_project, dim3(ncC), dim3(AI_BLOCK), 0, sw, (const Task*)coarseC.p, (const SegRec*)wrecC.p, (const double*)u1.p,
+                           slabs[0], (const double2*)pB1.p, pB0.p, gate, w_nbin);
+        AI_KERNEL_CHECK();
+      }
       hipLaunchKernelGGL(fk_set_flags, dim3((nfC + AI_BLOCK - 1) / AI_BLOCK), dim3(AI_BLOCK), 0, sw, (const Task*)fineC.p, nfC, factive.p, gate, w_nbin);
       AI_KERNEL_CHECK();
     }

@@ -584,12 +584,13 @@ __global__ __launch_bounds__(AI_BLOCK) void fk_pca_fill(const Task* __restrict__
 __global__ __launch_bounds__(AI_BLOCK) void fk_lz_init(const Task* __restrict__ ctasks, const SegRec* __restrict__ recs, FlowCsr G,
                                                        const double* __restrict__ u1, double* __restrict__ R0, double2* __restrict__ pB0,
                                                        int32_t* __restrict__ cactive, const int32_t* __restrict__ gate, int nbin,
-                                                       const double* __restrict__ warm) {
+                                                       const double* __restrict__ warm, double2* __restrict__ pBw) {
   __shared__ double sm[AI_BLOCK / 64];
   const Task tk = ctasks[blockIdx.x];
   if (tk.z < nbin && gate[tk.z] != 1) return;
   R0 += recs[tk.z].vdelta;
   const int wn = warm ? recs[tk.z].pad0 : 0;
+  if (wn > 0) pB0 = pBw;  // a start that carries a warm vector passes fk_lz_project, which reads all of the segment's partials
   const double wscale = sqrt((double)wn);
   const int32_t* __restrict__ orig = G.orig[FK_PAR(tk)];
   double nn = 0.0, gg = 0.0;
@@ -606,6 +607,48 @@ __global__ __launch_bounds__(AI_BLOCK) void fk_lz_init(const Task* __restrict__ 
     pB0[tk.w >> 2] = make_double2(tn, tg);
     ai_st_agent(&cactive[tk.w >> 2], 1);
   }
+}
+// A warm vector can be all but parallel to the segment's u1: the second Ritz vector of an ancestor is all but constant times sqrt(d)
+// on a block that ancestor cut off along a weak bridge.  Step 0 of fk_update takes b_0^2 = R.R - (u1.R)^2 and alpha_0 from
+// R.MR - (u1.R)^2, which then cancel: with 1e-7 of R.R left, the first Lanczos vector's norm is off by 5e-9, and a solve that would
+// take 9 steps stalls at residuals of 1e-7 until its Krylov space is exhausted (tests/csr_cases.py BAND; the NumPy model shows the
+// same with that norm).  So where less than a hundredth of R.R is left, u1 is taken out of R_0 here, once, before the first step,
+// and the partials are those of the projected vector; every other start goes on unchanged, bit for bit.  The decision is made
+// from the segment's own partials in a fixed order: a chunk cut in a batch decides as the chunk cut alone.
+// pBw: the partials fk_lz_init wrote for segments with a warm vector (read by every block of the segment); pB0: where step 0 reads.
+__global__ __launch_bounds__(AI_BLOCK) void fk_lz_project(const Task* __restrict__ ctasks, const SegRec* __restrict__ recs,
+                                                          const double* __restrict__ u1, double* __restrict__ R0,
+                                                          const double2* __restrict__ pBw, double2* __restrict__ pB0,
+                                                          const int32_t* __restrict__ gate, int nbin) {
+  __shared__ double sm[AI_BLOCK / 64];
+  const Task tk = ctasks[blockIdx.x];
+  if (tk.z < nbin && gate[tk.z] != 1) return;
+  const SegRec sr = recs[tk.z];
+  if (sr.pad0 <= 0) return;  // no warm vector: fk_lz_init wrote pB0 itself
+  double nn = 0.0, g = 0.0;
+  for (int t = sr.c0 + threadIdx.x; t < sr.c0 + FK_NC(sr); t += AI_BLOCK) {
+    const double2 v = pBw[t];
+    nn += v.x;
+    g += v.y;
+  }
+  nn = ai_block_sum(nn, sm);
+  g = ai_block_sum(g, sm);
+  if (!(nn - g * g < 1e-2 * nn)) {  // (also a sum that is not finite: left to the solve as before)
+    if (threadIdx.x == 0) pB0[tk.w >> 2] = pBw[tk.w >> 2];
+    return;
+  }
+  R0 += sr.vdelta;
+  double n2 = 0.0, g2 = 0.0;
+  for (int row = tk.x + threadIdx.x; row < tk.y; row += AI_BLOCK) {
+    const double u = u1[row];
+    const double r = fma(-g, u, R0[row]);
+    R0[row] = r;
+    n2 = fma(r, r, n2);
+    g2 = fma(u, r, g2);
+  }
+  const double tn = ai_block_sum(n2, sm);
+  const double tg = ai_block_sum(g2, sm);
+  if (threadIdx.x == 0) pB0[tk.w >> 2] = make_double2(tn, tg);
 }
 __global__ __launch_bounds__(AI_BLOCK) void fk_set_flags(const Task* __restrict__ ftasks, int n, int32_t* __restrict__ factive,
                                                          const int32_t* __restrict__ gate, int nbin) {

@@ -80,6 +80,19 @@ def last_stats() -> dict | None:
     return _last_stats
 
 
+def _has_duplicates(w: sp.csr_matrix) -> bool:
+    """Whether a CSR matrix stores some (row, col) twice; reads the arrays (not SciPy's cached flags) and changes nothing."""
+    if w.nnz < 2:
+        return False
+    step_ok = np.diff(w.indices) > 0
+    starts = w.indptr[1:-1]
+    step_ok[starts[(starts > 0) & (starts < w.nnz)] - 1] = True     # the step from one row into the next
+    if step_ok.all():
+        return False                                                # every row ascends strictly
+    key = np.repeat(np.arange(w.shape[0], dtype=np.int64), np.diff(w.indptr)) * w.shape[1] + w.indices
+    return np.unique(key).shape[0] != key.shape[0]
+
+
 class DeviceGraph:
     """Symmetric affinity graph resident in HBM (``ai_csr``)."""
 
@@ -93,10 +106,18 @@ class DeviceGraph:
 
     @classmethod
     def from_scipy(cls, w, ctx: Context | None = None) -> "DeviceGraph":
+        """Upload a SciPy matrix (``ai_csr_from_host``).  SciPy defines a matrix by its value, the device entry by what is
+        stored, so duplicate entries are summed and stored zeros dropped here, on a copy; a matrix that has neither goes up as it
+        is stored, columns unsorted included.  Values that are not finite or negative and a matrix that is not symmetric to the bit
+        raise ``ValueError`` with the library's message ("The caller's CSR at the door")."""
         ctx = ctx or default_context()
         w = sp.csr_matrix(w)
         if w.shape[0] != w.shape[1]:
             raise ValueError("affinity matrix must be square")
+        if np.any(w.data == 0) or _has_duplicates(w):
+            w = w.copy()
+            w.sum_duplicates()
+            w.eliminate_zeros()
         indptr = np.ascontiguousarray(w.indptr, dtype=np.int64)
         indices = np.ascontiguousarray(w.indices, dtype=np.int32)
         data = np.ascontiguousarray(w.data, dtype=np.float64)

@@ -126,6 +126,20 @@ int ai_affinity_build_batch(ai_ctx* ctx, const double* xyz, const int64_t* off, 
 /*
  * Upload a caller-built symmetric CSR (what ncuts_utils.py:167 hands to
  * normalized_cut at :168).  indptr has n+1 entries.  Row order is kept.
+ *
+ * The contract.  The cut reads the STORED entries (its connected components never look at a value, and a row trusts the other
+ * row's copy of an edge), the reference is defined by the matrix's VALUE; the two agree only on a graph that keeps these rules,
+ * so everything else is refused with AI_ERR_BAD_ARG and a message that starts "ai_csr_from_host:" and names the first offending
+ * row and column:
+ *   - a value that is not finite, a negative value, a stored zero of either sign;
+ *   - a second entry with the same (row, col) -- duplicates are not summed;
+ *   - an entry (i, j) whose mirror (j, i) is missing, or whose mirror's value differs in any bit.
+ * Accepted exactly as stored (nothing is sorted or rewritten): any column order within a row; a diagonal that is present, absent
+ * or partial, with any positive value (the cut adds the reference's identity on top of it); empty rows.
+ * Values and duplicates are judged on the host before anything is allocated.  Mirrors: on the host too when some row's columns do
+ * not ascend as stored; otherwise by one kernel on the uploaded copy, which is released again on refusal.  Either way a refused
+ * graph leaves *out unwritten and ai_ctx_mem_info's out[2] as it was, and the context serves the next call.
+ * Graphs built on the device (ai_affinity_build*) do not pass this door.
  */
 int ai_csr_from_host(ai_ctx* ctx, int64_t n, const int64_t* indptr, const int32_t* indices,
                      const double* data, ai_csr** out);
@@ -134,7 +148,8 @@ int ai_csr_dims(const ai_csr* csr, int64_t* n, int64_t* nnz);
 
 /*
  * Copy the graph out as scipy.sparse.csr_matrix(A) would hold it: rows and columns in
- * the caller's ORIGINAL point order, column indices ascending within a row.
+ * the caller's ORIGINAL point order, column indices ascending within a row.  (A graph from
+ * ai_csr_from_host comes back as it was stored, bit for bit, whatever its column order.)
  * indptr: n+1, indices/data: nnz (host buffers).
  */
 int ai_csr_export(ai_ctx* ctx, const ai_csr* csr, int64_t* indptr, int32_t* indices, double* data);

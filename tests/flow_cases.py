@@ -54,6 +54,14 @@ def build(case):
         tarl[::9] = 0.0
         g = api.build_affinity(pts, tarl, alpha=1.0, theta=0.5, gamma=0.0)
         return [g], [g.n], 0.03, SPLIT_LIM
+    if case in CSR_CASES:
+        # hand-built graphs whose rows, 32-row tasks and segments sit on the kernels' thresholds (tests/csr_cases.py).  `band` runs with
+        # num_points_orig = n and a root split_lim of 0.001: its 3-row block then stays unsolved, and that block is the one segment of
+        # these graphs with two mirror-image masks of equal cost (tests/test_csr_cases.py), which the per-record checks count as a near-tie
+        import csr_cases
+        w = csr_cases.limit_case(case)
+        n_orig, lim = (w.shape[0], 0.001) if case == "band" else (csr_cases.N_ORIG, csr_cases.SPLIT_LIM)
+        return [api.DeviceGraph.from_scipy(w)], [n_orig], csr_cases.T, lim
     raise ValueError(case)
 
 
@@ -68,7 +76,8 @@ def build_batch():
     return gs, [g.n for g in gs], HEADLINE["T"], SPLIT_LIM
 
 
-CASES = golden_names() + ["c1_10k_tarl", "c1_10k_spatial", "headline", "dense"]
+CSR_CASES = ("band", "band128", "band128_diag", "stride", "stride_diag")
+CASES = golden_names() + ["c1_10k_tarl", "c1_10k_spatial", "headline", "dense"] + list(CSR_CASES)
 
 
 def _save(out, name, graphs, n_orig, T, split_lim, labs, st):
