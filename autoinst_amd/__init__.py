@@ -13,7 +13,8 @@ def __getattr__(name):
                 "CutTree", "ncuts_tree", "ncuts_tree_batch", "relabel", "normalized_cut_sweep"):
         from . import ncuts_api as _n
         return getattr(_n, name)
-    if name in ("Metrics", "score", "label_pairs", "merge_chunks_unite_instances2", "merge_associate", "unique_points", "merge_map"):
+    if name in ("Metrics", "score", "label_pairs", "merge_chunks_unite_instances2", "merge_associate", "unique_points", "merge_map",
+                "label_tables", "remove_semantics", "score_sweep"):
         from . import labels_api as _l
         return getattr(_l, name)
     if name in ("box_select", "statistical_inlier_indices", "voxel_down_sample", "chunks_from_pointcloud",

@@ -24,28 +24,6 @@
 
 namespace {
 
-// ------------------------------------------------------------------ label pairs
-__global__ __launch_bounds__(AI_BLOCK) void kl_pair_keys(const int32_t* __restrict__ a, const int32_t* __restrict__ b, int64_t n,
-                                                         uint64_t* __restrict__ key) {
-  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  key[i] = ((uint64_t)((uint32_t)a[i] ^ 0x80000000u) << 32) | (uint64_t)((uint32_t)b[i] ^ 0x80000000u);
-}
-
-// one thread per sorted element: a run's head writes the run's key and start
-__global__ __launch_bounds__(AI_BLOCK) void kl_pair_emit(const uint64_t* __restrict__ key, const int32_t* __restrict__ pos, int64_t n,
-                                                         int32_t* __restrict__ out_a, int32_t* __restrict__ out_b,
-                                                         int32_t* __restrict__ start) {
-  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  if (pos[i + 1] == pos[i]) return;
-  const int64_t r = pos[i];
-  const uint64_t k = key[i];
-  out_a[r] = (int32_t)((uint32_t)(k >> 32) ^ 0x80000000u);
-  out_b[r] = (int32_t)((uint32_t)k ^ 0x80000000u);
-  start[r] = (int32_t)i;
-}
-
 // ------------------------------------------------------------------ merge association
 struct Cube {
   double lo[3], hi[3];
@@ -242,24 +220,14 @@ extern "C" int ai_label_pairs(ai_ctx* ctx, const int32_t* a, const int32_t* b, i
   AI_HIP(hipSetDevice(ctx->device));
   ArenaScope arena_scope(&ctx->arena);
   hipStream_t st = ctx->stream;
-  DevBuf<int32_t> own_a, own_b, pos, scan_tmp, oa, ob, ostart;
-  DevBuf<uint64_t> key, skey;
-  DevBuf<uint8_t> tmp;
+  DevBuf<int32_t> own_a, own_b, oa, ob, ostart;
+  PairRuns runs;
   const int32_t *da, *db;
   AI_TRY(to_device(a, (size_t)n, mem_kind, own_a, &da, st));
   AI_TRY(to_device(b, (size_t)n, mem_kind, own_b, &db, st));
-  AI_TRY(key.alloc(n));
-  AI_TRY(skey.alloc(n));
-  AI_TRY(pos.alloc(n + 1));
-  hipLaunchKernelGGL(kl_pair_keys, dim3(grid_for(n)), dim3(AI_BLOCK), 0, st, da, db, n, key.p);
-  AI_KERNEL_CHECK();
-  size_t tmp_bytes = 0;
-  AI_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, key.p, skey.p, (size_t)n, 0, 64, st));
-  AI_TRY(tmp.alloc(tmp_bytes));
-  AI_HIP(rocprim::radix_sort_keys(tmp.p, tmp_bytes, key.p, skey.p, (size_t)n, 0, 64, st));
-  hipLaunchKernelGGL(kl_heads<uint64_t>, dim3(grid_for(n)), dim3(AI_BLOCK), 0, st, (const uint64_t*)skey.p, n, pos.p);
-  AI_KERNEL_CHECK();
-  AI_TRY(scan_flags(st, pos.p, n, scan_tmp));
+  AI_TRY(sorted_pair_runs(st, da, db, n, runs));
+  DevBuf<uint64_t>& skey = runs.skey;
+  DevBuf<int32_t>& pos = runs.pos;
   int32_t total = 0;
   AI_HIP(hipMemcpyAsync(&total, pos.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
   AI_HIP(hipStreamSynchronize(st));

@@ -62,6 +62,58 @@ __global__ __launch_bounds__(AI_BLOCK) void km_common(const uint64_t* __restrict
   }
 }
 
+// ------------------------------------------------------------------ label pairs by sorting (ai_label_pairs; the fallback of ai_label_tables)
+// one uint64 per point whose unsigned order is the signed order of (a, b)
+__host__ __device__ __forceinline__ uint64_t pair_key(int32_t a, int32_t b) {
+  return ((uint64_t)((uint32_t)a ^ 0x80000000u) << 32) | (uint64_t)((uint32_t)b ^ 0x80000000u);
+}
+__host__ __device__ __forceinline__ int32_t pair_key_a(uint64_t k) { return (int32_t)((uint32_t)(k >> 32) ^ 0x80000000u); }
+__host__ __device__ __forceinline__ int32_t pair_key_b(uint64_t k) { return (int32_t)((uint32_t)k ^ 0x80000000u); }
+
+__global__ __launch_bounds__(AI_BLOCK) void kl_pair_keys(const int32_t* __restrict__ a, const int32_t* __restrict__ b, int64_t n,
+                                                         uint64_t* __restrict__ key) {
+  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  key[i] = pair_key(a[i], b[i]);
+}
+
+// one thread per sorted element: a run's head writes the run's key and start
+__global__ __launch_bounds__(AI_BLOCK) void kl_pair_emit(const uint64_t* __restrict__ key, const int32_t* __restrict__ pos, int64_t n,
+                                                         int32_t* __restrict__ out_a, int32_t* __restrict__ out_b,
+                                                         int32_t* __restrict__ start) {
+  const int64_t i = (int64_t)blockIdx.x * AI_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  if (pos[i + 1] == pos[i]) return;
+  const int64_t r = pos[i];
+  const uint64_t k = key[i];
+  out_a[r] = pair_key_a(k);
+  out_b[r] = pair_key_b(k);
+  start[r] = (int32_t)i;
+}
+
+// The sorted keys of n > 0 points and, per sorted position, the number of runs before it (pos[n]: the number of distinct pairs).
+// Everything is queued on `st`; nothing is waited for.
+struct PairRuns {
+  DevBuf<uint64_t> key, skey;
+  DevBuf<int32_t> pos, scan_tmp;
+  DevBuf<uint8_t> tmp;
+};
+int sorted_pair_runs(hipStream_t st, const int32_t* da, const int32_t* db, int64_t n, PairRuns& r) {
+  AI_TRY(r.key.ensure(n));
+  AI_TRY(r.skey.ensure(n));
+  AI_TRY(r.pos.ensure(n + 1));
+  hipLaunchKernelGGL(kl_pair_keys, dim3(grid_for(n)), dim3(AI_BLOCK), 0, st, da, db, n, r.key.p);
+  AI_KERNEL_CHECK();
+  size_t tmp_bytes = 0;
+  AI_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, r.key.p, r.skey.p, (size_t)n, 0, 64, st));
+  AI_TRY(r.tmp.ensure(tmp_bytes));
+  AI_HIP(rocprim::radix_sort_keys(r.tmp.p, tmp_bytes, r.key.p, r.skey.p, (size_t)n, 0, 64, st));
+  hipLaunchKernelGGL(kl_heads<uint64_t>, dim3(grid_for(n)), dim3(AI_BLOCK), 0, st, (const uint64_t*)r.skey.p, n, r.pos.p);
+  AI_KERNEL_CHECK();
+  AI_TRY(r.scan_tmp.ensure(ai_scan_tmp_elems(n)));
+  return ai_exclusive_scan_i32(st, r.pos.p, r.pos.p, n, r.scan_tmp.p);
+}
+
 // open3d keys an unordered_map on the Eigen vector: equality by value and std::hash<double>, which maps
 // -0.0 and +0.0 to the same bucket; every other pair of distinct bit patterns is a distinct point
 __device__ __forceinline__ uint64_t value_bits(double v) {

@@ -14,6 +14,10 @@ that results are bit-equal:
 `merge_map` is the same merge for a whole map in one resident device call (``csrc/ai_merge.hip``, rules M1-M10 of
 ``include/autoinst_hip.h``), with the instance id as the identity instead of the colour.
 
+`label_tables` is the scorer's per-point part for k label maps of one map in one device call (``csrc/ai_score.hip``, rules S1-S5):
+the k contingency tables with ``remove_semantics`` and ``filter_labels`` decided per label; `remove_semantics`, `score_sweep` and
+`Metrics.update_stats` on device tensors go through it.
+
 There is no CPU fallback: every function raises when the HIP library or a gfx950 device is missing.
 """
 from __future__ import annotations
@@ -142,10 +146,8 @@ def _s_assoc(table, min_points):
     return outer / int(g_keep.sum())
 
 
-def score(all_labels, pred_labels, gt_labels, min_points=200, *, ctx: Context | None = None):
-    """One ``Metrics.update_stats`` on a fresh scorer: dict(p, r, f1, ap, ap0.25, ap0.5, S_assoc)."""
-    pred = _Table(*label_pairs(pred_labels, gt_labels, ctx=ctx)).filtered(min_points)
-    alll = pred if all_labels is pred_labels else _Table(*label_pairs(all_labels, gt_labels, ctx=ctx)).filtered(min_points)
+def _score_tables(pred, alll, min_points):
+    """The instance-level arithmetic of one ``update_stats`` from the two filtered tables."""
     iou = _iou(pred)
     tps = int(sum(_greedy(pred, iou, 0.5)))
     n_pred = int((pred.rows != 0).sum())
@@ -162,6 +164,126 @@ def score(all_labels, pred_labels, gt_labels, min_points=200, *, ctx: Context | 
             "S_assoc": _s_assoc(alll, min_points), "tps": tps, "n_pred": n_pred, "n_gt": n_gt}
 
 
+def score(all_labels, pred_labels, gt_labels, min_points=200, *, ctx: Context | None = None):
+    """One ``Metrics.update_stats`` on a fresh scorer: dict(p, r, f1, ap, ap0.25, ap0.5, S_assoc)."""
+    if any(_is_device_tensor(a) for a in (all_labels, pred_labels, gt_labels)):
+        return _score_resident(all_labels, pred_labels, gt_labels, min_points, ctx)
+    pred = _Table(*label_pairs(pred_labels, gt_labels, ctx=ctx)).filtered(min_points)
+    alll = pred if all_labels is pred_labels else _Table(*label_pairs(all_labels, gt_labels, ctx=ctx)).filtered(min_points)
+    return _score_tables(pred, alll, min_points)
+
+
+# ----------------------------------------------------------------------------- k label maps in one call
+def _stack_rows(preds, gt):
+    """(place, (k, n) int32 buffer, n int32 buffer) of the label maps and the ground truth.  ``preds``: one (k, n) array or tensor,
+    or a list of k one-dimensional ones; a row that is itself a list (`relabel`'s per-chunk views of one threshold) is concatenated."""
+    if isinstance(preds, (list, tuple)):
+        rows = list(preds)
+    elif getattr(preds, "ndim", None) == 2:
+        if _is_device_tensor(preds) and not preds.is_floating_point():   # already one buffer: no row is copied on its own
+            place = place_of(preds)
+            g = cat_int32([gt if _is_device_tensor(gt) else _as_i32(gt, "gt")], place)
+            if int(preds.shape[1]) != int(g.shape[0]):
+                raise ValueError("label_tables: every label map must have one label per ground-truth point")
+            return place, preds.to(dtype=place.dtype(np.int32)).contiguous(), g
+        rows = [preds[t] for t in range(int(preds.shape[0]))]
+    else:
+        raise ValueError("label_tables: preds must be a (k, n) array or tensor, or a list of k label arrays")
+    place = place_of(gt, *[x for r in rows for x in (r if isinstance(r, (list, tuple)) else (r,))])
+    flat = []
+    for t, r in enumerate(rows):
+        parts = list(r) if isinstance(r, (list, tuple)) else [r]
+        for a in parts:
+            if _is_device_tensor(a) and (a.is_floating_point() or a.dim() != 1):
+                raise ValueError(f"label_tables: preds[{t}] must be one-dimensional integers")
+        flat.append(cat_int32([a if _is_device_tensor(a) else _as_i32(a, f"preds[{t}]") for a in parts], place))
+    g = cat_int32([gt if _is_device_tensor(gt) else _as_i32(gt, "gt")], place)
+    n = int(g.shape[0])
+    if any(int(f.shape[0]) != n for f in flat):
+        raise ValueError("label_tables: every label map must have one label per ground-truth point")
+    if place.device is not None:
+        import torch
+        stacked = torch.stack(flat).contiguous() if flat else place.zeros((0, n), np.int32)
+    else:
+        stacked = np.ascontiguousarray(np.stack(flat)) if flat else np.zeros((0, n), np.int32)
+    return place, stacked, g
+
+
+def label_tables(preds, gt, *, threshold=0.8, min_points=200, return_labels=False, ctx: Context | None = None):
+    """What the scorer needs of k label maps against one ground truth, in one device call (``ai_label_tables``, rules S1-S5 of
+    ``include/autoinst_hip.h``).
+
+    ``preds``: a (k, n) array or tensor, a list of k label arrays, or `ncuts_api.relabel`'s per-threshold buffers; ``gt``: n labels.
+    On the host or on one GPU.  Returns a list of k tables ``(pred, gt, count, removed, small)``: the distinct pairs of row t in
+    ascending order with their int64 counts, and per pair whether ``remove_semantics`` at ``threshold`` removes its label and
+    whether ``filter_labels`` at ``min_points`` finds it small.  With ``return_labels`` also ``pred_removed`` and ``pred_scored``,
+    (k, n) int32 where the inputs live: the labels after the removal, and after the removal and the filter."""
+    ctx = ctx or default_context()
+    place, p, g = _stack_rows(preds, gt)
+    k, n = int(p.shape[0]), int(g.shape[0])
+    rem = place.new((k, n), np.int32) if return_labels else None
+    sco = place.new((k, n), np.int32) if return_labels else None
+    off = np.zeros(k + 1, dtype=np.int64)
+    lib, mem = _ffi.load(), place.mem
+
+    def tables(cap):
+        pa, pb, cnt, fl = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.int64), np.empty(cap, np.uint8)
+        place.sync()
+        _ffi.check(lib.ai_label_tables(ctx._h, place.addr_or_null(p), place.addr_or_null(g), k, n, float(threshold), int(min_points),
+                                       mem, cap, pa.ctypes.data, pb.ctypes.data, cnt.ctypes.data, fl.ctypes.data, off.ctypes.data,
+                                       place.addr_or_null(rem), place.addr_or_null(sco)), "ai_label_tables")
+        return int(off[k]), (pa, pb, cnt, fl)
+    _, (pa, pb, cnt, fl) = grow(tables, 1 << 16)
+    out = []
+    for t in range(k):
+        s = slice(int(off[t]), int(off[t + 1]))
+        out.append((pa[s].copy(), pb[s].copy(), cnt[s].copy(), (fl[s] & 1).astype(bool), (fl[s] & 2).astype(bool)))
+    return (out, rem, sco) if return_labels else out
+
+
+def remove_semantics(labels, preds, threshold=0.8, num_threads=4, *, ctx: Context | None = None):
+    """``point_cloud_utils.py:260-287`` with the reference's argument order (``labels`` is the ground truth) and return value: a copy
+    of ``preds`` in which every label whose points lie on ground truth 0 by more than ``threshold`` of their number is 0 -- an array
+    of ``preds``' dtype, or a tensor where ``preds`` lives.  ``num_threads`` is accepted and ignored."""
+    _, rem, _ = label_tables([preds], labels, threshold=threshold, min_points=0, return_labels=True, ctx=ctx)
+    if _is_device_tensor(preds):
+        return rem[0].to(device=preds.device, dtype=preds.dtype)
+    if _is_device_tensor(rem):
+        rem = rem.cpu().numpy()
+    return rem[0].astype(np.asarray(preds).dtype)
+
+
+def _flagged_table(pa, pb, cnt, zero):
+    """The contingency table of a label map whose labels flagged in ``zero`` (per pair) are 0."""
+    return _Table(np.where(zero, 0, pa).astype(np.int32), pb, cnt)
+
+
+def _sweep_scores(tables, min_points, remove):
+    out = []
+    for pa, pb, cnt, removed, small in tables:
+        alll = _flagged_table(pa, pb, cnt, small)
+        pred = _flagged_table(pa, pb, cnt, removed | small) if remove else alll
+        out.append(_score_tables(pred, alll, min_points))
+    return out
+
+
+def score_sweep(preds, gt, min_points=200, *, remove=True, threshold=0.8, ctx: Context | None = None):
+    """`score` of k label maps against one ground truth from one `label_tables` call: a list of k dicts.  With ``remove`` dict t is
+    ``score(preds[t], remove_semantics(gt, preds[t], threshold), gt, min_points)``, lines 223-238 of the reference's loop; without,
+    ``score(preds[t], preds[t], gt, min_points)``.  The tables the host arithmetic runs on are formed from the flagged pairs (rule
+    S4); no label array crosses to the host."""
+    return _sweep_scores(label_tables(preds, gt, threshold=threshold, min_points=min_points, ctx=ctx), min_points, remove)
+
+
+def _score_resident(all_labels, pred_labels, gt_labels, min_points, ctx):
+    """`score` for label arrays of which at least one is a device tensor: the filtered tables of both from one `label_tables` call."""
+    same = all_labels is pred_labels
+    tables = label_tables([pred_labels] if same else [pred_labels, all_labels], gt_labels, threshold=0.0, min_points=min_points, ctx=ctx)
+    pred = _flagged_table(*tables[0][:3], tables[0][4])
+    alll = pred if same else _flagged_table(*tables[-1][:3], tables[-1][4])
+    return _score_tables(pred, alll, min_points)
+
+
 class Metrics:
     """The reference's scorer object (``metrics_class.py:15``): same constructor arguments,
     ``update_stats`` signature, return value and ``sequence_metrics`` bookkeeping; precision /
@@ -176,6 +298,7 @@ class Metrics:
         self.sequence_metrics = {'ap0.5': [], 'ap0.25': [], 'ap': [], 'p': [], 'r': [], 'f1': [], 'S_assoc': []}
 
     def update_stats(self, all_labels, pred_labels, gt_labels, confs=[], calc_all=True, calc_lstq=True):
+        """Host arrays go through `label_pairs`; with a device tensor among the three the labels stay where they are (`label_tables`)."""
         if len(confs):
             raise NotImplementedError("per-instance confidences are never passed by the reference pipeline")
         s = score(all_labels, pred_labels, gt_labels, self.min_points, ctx=self._ctx)

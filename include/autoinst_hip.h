@@ -353,6 +353,41 @@ int ai_merge_associate(ai_ctx* ctx, const double* map_xyz, const int32_t* map_in
 int ai_unique_points(ai_ctx* ctx, const double* xyz, int64_t n, int mem_kind, int32_t* keep_index, int64_t* n_keep);
 
 /*
+ * The tail of the reference's loop (run_pipeline.py:214-238) for k label maps at once: what the scorer needs of k predictions of one
+ * map against one ground truth, with remove_semantics (pipeline/utils/point_cloud/point_cloud_utils.py:249-287, called at
+ * run_pipeline.py:223) applied by the reference's rule.  pred: k x n int32, row-major -- the layout
+ * ai_ncut_relabel writes; gt: n int32; both host or device per mem_kind.  Every int32 value is a legal label, as for ai_label_pairs.
+ *   S1  Tables.  For every row t the distinct pairs (pred[t][i], gt[i]) with their int64 counts, in ascending (pred, gt) order: row
+ *       t of the call equals ai_label_pairs(pred[t], gt) exactly.  The rows stand behind each other; row t is the pairs
+ *       row_off[t] .. row_off[t + 1] - 1.
+ *   S2  Removal (remove_semantics).  For a label u of row t let m = #{i : pred[t][i] == u} and z = #{i : pred[t][i] == u and
+ *       gt[i] == 0}.  u is removed iff (double)z > threshold * (double)m: one float64 multiply and one strict comparison, the
+ *       reference's `cur_intersect > threshold * len(pred_idcs)`.  Label 0 takes part like any other label; removing it changes
+ *       nothing.  pred_removed[t][i] = 0 where the label of the point is removed, pred[t][i] elsewhere.  Rows do not see each other.
+ *   S3  Small labels (filter_labels, pipeline/metrics/metrics_class.py:302-309).  u is small iff m < min_points.  The scorer filters
+ *       AFTER the removal, this entry decides on the labels as given, and that is the same: the removal moves whole labels to 0, so
+ *       a label u != 0 that survives it keeps every one of its m points and gains none -- it is small after iff it was small before
+ *       -- and a removed label no longer exists.  Only label 0 grows, and whether 0 is small makes no difference: a small label
+ *       becomes 0.
+ *   S4  What the scorer sees.  `all` is pred with the small labels set to 0; `scored` is pred with the removed or small labels set
+ *       to 0 (pred_scored).  Every pair carries the flags of its label, pair_flags bit 0 = removed and bit 1 = small, so the host
+ *       forms both contingency tables by uniting the rows of the flagged labels with label 0's: no second pass over the points.
+ *   S5  Limits and errors.  1 <= k <= 64, n < 2^31 - 1, threshold finite and >= 0, min_points >= 0; any of them violated is
+ *       AI_ERR_BAD_ARG with no output written.  n == 0 is no error: every row has zero pairs.  pair_pred / pair_gt / pair_count /
+ *       pair_flags are HOST arrays of capacity `cap`; row_off (HOST, k + 1 entries) is always filled with the full counts: call again
+ *       when row_off[k] > cap, as with ai_label_pairs.  Then exactly the leading cap pairs are written and nothing beyond them.
+ *       pred_removed and pred_scored (k x n, placed per mem_kind, each may be NULL) are written in full whatever cap is.
+ * A row is counted in hash tables (block-local in LDS, then one 64-bit atomic add per distinct pair and block) of 8192 and, when it
+ * has more than 4096 distinct pairs, 131072 slots; a row with more than 65536 distinct pairs goes through ai_label_pairs' sort.  The
+ * result does not depend on the path a row took: counts are integers, and every row's pairs are sorted at the end.
+ * Host synchronisations: two when every row fits its first table (the rows' sizes, the result); one more when a row needs the
+ * second table, and one more -- for all such rows together -- when a row needs the sort.  At most four, whatever k is.
+ */
+int ai_label_tables(ai_ctx* ctx, const int32_t* pred, const int32_t* gt, int32_t k, int64_t n, double threshold, int64_t min_points,
+                    int mem_kind, int64_t cap, int32_t* pair_pred, int32_t* pair_gt, int64_t* pair_count, uint8_t* pair_flags,
+                    int64_t* row_off, int32_t* pred_removed, int32_t* pred_scored);
+
+/*
  * The step that produces the chunks: chunk_and_downsample_point_clouds (pipeline/dataset/dataset_utils.py:489-567, called at
  * run_pipeline.py:129), per chunk and per cloud (non-ground / ground).  xyz and the index / point outputs are host or device
  * according to mem_kind; counts, offsets and stats are HOST values.  Indices are int32 (n < 2^30; box select: n < 2^31 - 256).
