@@ -14,7 +14,7 @@ def __getattr__(name):
         from . import ncuts_api as _n
         return getattr(_n, name)
     if name in ("Metrics", "score", "label_pairs", "merge_chunks_unite_instances2", "merge_associate", "unique_points", "merge_map",
-                "label_tables", "remove_semantics", "score_sweep"):
+                "label_tables", "remove_semantics", "score_sweep", "label_scores"):
         from . import labels_api as _l
         return getattr(_l, name)
     if name in ("box_select", "statistical_inlier_indices", "voxel_down_sample", "chunks_from_pointcloud",

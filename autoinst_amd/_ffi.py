@@ -26,7 +26,7 @@ SYMBOLS = (
     "ai_box_select", "ai_statistical_inliers", "ai_voxel_down_sample", "ai_camera_project",
     "ai_voxel_down_sample_nearest", "ai_scan_pool", "ai_aggregate_scans", "ai_chunk_finish", "ai_merge_map",
     "ai_ground_planes", "ai_ncut_tree", "ai_ncut_tree_batch", "ai_ncut_relabel", "ai_hidden_points",
-    "ai_dbscan", "ai_affinity_build_batch", "ai_label_tables",
+    "ai_dbscan", "ai_affinity_build_batch", "ai_label_tables", "ai_label_scores",
 )
 ABI_VERSION = 6   # AI_ABI_VERSION of the header this binding was written against
 
@@ -130,7 +130,8 @@ def load():
                        ("ai_hidden_points", [vp, vp, i64, vp, i64, vp, i32, dbl, C.c_int, vp, vp, vp, vp]),
                        ("ai_dbscan", [vp, vp, vp, i32, dbl, i32, C.c_int, vp, vp, vp, vp]),
                        ("ai_affinity_build_batch", [vp, vp, vp, i32, vp, i32, vp, i32, dbl, dbl, dbl, dbl, i64, C.c_int, P(vp)]),
-                       ("ai_label_tables", [vp, vp, vp, i32, i64, dbl, i64, C.c_int, i64] + [vp] * 7)):
+                       ("ai_label_tables", [vp, vp, vp, i32, i64, dbl, i64, C.c_int, i64] + [vp] * 7),
+                       ("ai_label_scores", [vp, vp, vp, i32, i64, dbl, i64, C.c_int, i32, vp, i32, i64] + [vp] * 5)):
         if hasattr(lib, name):   # an older build selected for an A/B run may lack them
             getattr(lib, name).argtypes = args
     if os.environ.get("AUTOINST_HIP_LIB") and not hasattr(lib, "ai_abi_version"):

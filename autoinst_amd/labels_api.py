@@ -18,6 +18,10 @@ that results are bit-equal:
 the k contingency tables with ``remove_semantics`` and ``filter_labels`` decided per label; `remove_semantics`, `score_sweep` and
 `Metrics.update_stats` on device tensors go through it.
 
+`label_scores` is the scorer's instance-level part for the same k label maps on the device (``ai_label_scores``, rules Q1-Q8): the
+greedy matching at every overlap and S_assoc from the rows' sorted pairs; the host forms AP from one hit flag per overlap and scored
+label.  `score_sweep` uses it by default, and so do `score` / `Metrics.update_stats` on device tensors.
+
 There is no CPU fallback: every function raises when the HIP library or a gfx950 device is missing.
 """
 from __future__ import annotations
@@ -267,21 +271,92 @@ def _sweep_scores(tables, min_points, remove):
     return out
 
 
-def score_sweep(preds, gt, min_points=200, *, remove=True, threshold=0.8, ctx: Context | None = None):
-    """`score` of k label maps against one ground truth from one `label_tables` call: a list of k dicts.  With ``remove`` dict t is
+def _ap_from_hits(hits, n_gt_labels):
+    """``average_precision`` (``metrics_class.py:181-235``, every confidence 0.5) from the hit flags of the scored labels in matching
+    order (rule Q5) and the number of non-zero ground-truth labels: the precision / recall lists of `_average_precision` as arrays,
+    summed by the same ``trapz``."""
+    n = int(hits.size)
+    if n and not n_gt_labels:
+        raise ZeroDivisionError("float division by zero")         # `tp / float(tp + fn)` of the first scored label
+    tp = np.cumsum(hits, dtype=np.int64)
+    precision = np.concatenate([[1.0], tp / np.arange(1, n + 1, dtype=np.float64)])
+    recall = np.concatenate([[0.0], tp / np.float64(max(n_gt_labels, 1))])
+    trapz = getattr(np, "trapezoid", None) or np.trapz
+    return float(trapz(precision, recall))
+
+
+def _score_from_hits(hits, n_pred, n_gt_labels, gt_zero, tps, s_assoc):
+    """`_score_tables`' dict from what ``ai_label_scores`` returns for one row: ``hits`` (len(OVERLAPS), n_pred) flags, the counts of
+    rule Q6, the hits at overlap 0.5 and S_assoc."""
+    n_gt = n_gt_labels if gt_zero else 0                                # calculate_full_stats:323-325
+    prec = tps / n_pred if n_pred else float("nan")
+    rec = tps / n_gt if n_gt else float("nan")
+    try:
+        f1 = 2 * (prec * rec) / (prec + rec)
+    except ZeroDivisionError:
+        f1 = 0
+    aps = {o: _ap_from_hits(hits[j], n_gt_labels) for j, o in enumerate(OVERLAPS)}
+    ap = sum(aps[o] for o in AP_OVERLAPS) / float(len(AP_OVERLAPS))
+    return {"p": prec, "r": rec, "f1": f1, "ap": ap, "ap0.25": aps[0.25], "ap0.5": aps[0.5],
+            "S_assoc": s_assoc, "tps": tps, "n_pred": n_pred, "n_gt": n_gt}
+
+
+def _device_scores(preds, gt, threshold, min_points, remove, ctx):
+    """``ai_label_scores`` at `OVERLAPS`: per row ``(hits (len(OVERLAPS), n_pred) uint8, n_pred, distinct gt != 0, whether gt 0 occurs,
+    hits at 0.5, S_assoc)``, the arguments of `_score_from_hits`."""
+    ctx = ctx or default_context()
+    place, p, g = _stack_rows(preds, gt)
+    k, n = int(p.shape[0]), int(g.shape[0])
+    ov = np.asarray(OVERLAPS, dtype=np.float64)
+    no = int(ov.size)
+    hit_off, counts = np.zeros(k + 1, dtype=np.int64), np.zeros((k, 3), dtype=np.int32)
+    tp, sa = np.zeros((k, no), dtype=np.int32), np.zeros(k, dtype=np.float64)
+    lib, mem = _ffi.load(), place.mem
+
+    def scores(cap):
+        hits = np.empty(cap, np.uint8)
+        place.sync()
+        _ffi.check(lib.ai_label_scores(ctx._h, place.addr_or_null(p), place.addr_or_null(g), k, n, float(threshold), int(min_points), mem,
+                                       1 if remove else 0, ov.ctypes.data, no, cap, hits.ctypes.data, hit_off.ctypes.data,
+                                       counts.ctypes.data, tp.ctypes.data, sa.ctypes.data), "ai_label_scores")
+        return int(hit_off[k]) * no, hits
+    _, hits = grow(scores, 1 << 16)
+    half = OVERLAPS.index(0.5)
+    out = []
+    for t in range(k):
+        n_pred = int(counts[t, 0])
+        h = hits[int(hit_off[t]) * no:int(hit_off[t + 1]) * no].reshape(no, n_pred)
+        out.append((h, n_pred, int(counts[t, 1]), bool(counts[t, 2]), int(tp[t, half]), float(sa[t])))
+    return out
+
+
+def label_scores(preds, gt, *, threshold=0.8, min_points=200, remove=True, ctx: Context | None = None):
+    """`score` of k label maps against one ground truth with the instance-level arithmetic on the device (``ai_label_scores``, rules
+    Q1-Q8 of ``include/autoinst_hip.h``): a list of k dicts with `_score_tables`' keys.  ``preds`` and ``gt`` as for `label_tables`.
+    The greedy matching at every overlap and S_assoc are computed from the rows' sorted pairs where they lie; the host forms the
+    average precision from one hit flag per (overlap, scored label) -- NumPy's ``trapz`` is the reference's sum -- and p, r, f1."""
+    return [_score_from_hits(*row) for row in _device_scores(preds, gt, threshold, min_points, remove, ctx)]
+
+
+def score_sweep(preds, gt, min_points=200, *, remove=True, threshold=0.8, instance_level="device", ctx: Context | None = None):
+    """`score` of k label maps against one ground truth from one device call: a list of k dicts.  With ``remove`` dict t is
     ``score(preds[t], remove_semantics(gt, preds[t], threshold), gt, min_points)``, lines 223-238 of the reference's loop; without,
-    ``score(preds[t], preds[t], gt, min_points)``.  The tables the host arithmetic runs on are formed from the flagged pairs (rule
-    S4); no label array crosses to the host."""
+    ``score(preds[t], preds[t], gt, min_points)``.  No label array crosses to the host.  ``instance_level``: ``"device"`` is
+    `label_scores`; ``"host"`` takes the flagged pairs of `label_tables` to the host and runs the arithmetic there on dense tables
+    (rule S4) -- the same dicts, bit for bit."""
+    if instance_level == "device":
+        return label_scores(preds, gt, threshold=threshold, min_points=min_points, remove=remove, ctx=ctx)
+    if instance_level != "host":
+        raise ValueError("score_sweep: instance_level must be 'device' or 'host'")
     return _sweep_scores(label_tables(preds, gt, threshold=threshold, min_points=min_points, ctx=ctx), min_points, remove)
 
 
 def _score_resident(all_labels, pred_labels, gt_labels, min_points, ctx):
-    """`score` for label arrays of which at least one is a device tensor: the filtered tables of both from one `label_tables` call."""
+    """`score` for label arrays of which at least one is a device tensor: one ``ai_label_scores`` call without removal on the rows
+    [pred, all]; the matching is the pred row's, S_assoc the all row's."""
     same = all_labels is pred_labels
-    tables = label_tables([pred_labels] if same else [pred_labels, all_labels], gt_labels, threshold=0.0, min_points=min_points, ctx=ctx)
-    pred = _flagged_table(*tables[0][:3], tables[0][4])
-    alll = pred if same else _flagged_table(*tables[-1][:3], tables[-1][4])
-    return _score_tables(pred, alll, min_points)
+    rows = _device_scores([pred_labels] if same else [pred_labels, all_labels], gt_labels, 0.0, min_points, False, ctx)
+    return _score_from_hits(*rows[0][:5], rows[-1][5])
 
 
 class Metrics:

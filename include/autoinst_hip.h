@@ -388,6 +388,46 @@ int ai_label_tables(ai_ctx* ctx, const int32_t* pred, const int32_t* gt, int32_t
                     int64_t* row_off, int32_t* pred_removed, int32_t* pred_scored);
 
 /*
+ * The instance-level arithmetic of the scorer for the same k label maps, on the device: the greedy matching of get_tp_fp /
+ * average_precision (pipeline/metrics/metrics_class.py:60-114, :181-235) at every overlap and S_assoc (pipeline/metrics/
+ * modified_LSTQ.py:23-80) per row, from the sorted pairs ai_label_tables forms.  pred, gt, k, n, threshold,
+ * min_points and mem_kind are ai_label_tables'; remove != 0 scores the labels after remove_semantics, remove == 0 the labels as given
+ * (after filter_labels either way).  overlaps: HOST, n_overlaps float64 IoU thresholds (metrics_class.py:37).
+ *   Q1  Tables and flags.  Exactly S1-S3 of ai_label_tables on the same input.
+ *   Q2  Labels.  The scored labels of row t are the labels u != 0 whose flags have no bit of `mask` set, mask = removed | small with
+ *       remove and small without it, in ascending signed order; their number is n_pred.  Negative labels take part.  The association
+ *       labels are the labels u > 0 that are not small, whatever remove is.
+ *   Q3  Areas.  ap(u) is the m of rule S2.  ag(v) is the number of points with gt == v, the points of flagged labels included: the
+ *       column sum of the full table.
+ *   Q4  IoU of a stored pair (u, v, c): (double)c / (double)max(ap(u) + ag(v) - c, 1), one correctly rounded float64 division.  The
+ *       pair is a candidate at overlap o iff iou >= overlaps[o] and v != 0.  A pair that is not stored has IoU 0 and is no candidate.
+ *   Q5  Greedy match, per overlap independently.  The scored labels go in ascending order; a label takes the first of its
+ *       candidates, v ascending, that no earlier label of this overlap took -- a hit -- and a label with none left is a miss.  For
+ *       row t one byte (1 hit, 0 miss) per (overlap, scored label), overlap-major and in label order: byte
+ *       hit_off[t] * n_overlaps + o * n_pred + rank.
+ *   Q6  Integers per row.  row_counts[3 t + 0 .. 2] = n_pred, the number of distinct v != 0, whether v == 0 occurs (0 / 1);
+ *       tp[t * n_overlaps + o] = the hits of overlap o.
+ *   Q7  S_assoc per row (modified_LSTQ.py:23-80).  v is kept iff v != 0 and ag(v) > min_points; with no kept v the result is NaN.
+ *       inner(v) is 0.0 unless v > 0; then it is the sum, over the association labels u ascending that have a pair (u, v, c), of
+ *       (double)c * ((double)c / (double)(ag(v) + ap(u) - c)), added in that order starting from 0.0.  outer is the sum over the kept
+ *       v ascending of inner(v) / (double)ag(v), and s_assoc[t] = outer / (double)#kept.  Every operation is rounded once; nothing is
+ *       fused.
+ *   Q8  Limits and errors.  S5's limits; 1 <= n_overlaps <= 16; every overlap finite and in (0, 1] (an overlap above 0 is what lets
+ *       only stored pairs be candidates); any of them violated is AI_ERR_BAD_ARG with no output written.  n == 0 is no error: every row
+ *       gets zeros and a NaN s_assoc.  hit_off (k + 1 entries, in scored labels), row_counts (3 k), tp (k * n_overlaps) and s_assoc
+ *       (k) are HOST arrays and always complete.  hits (HOST, capacity cap bytes) follows the capacity rule of ai_label_pairs: call
+ *       again when hit_off[k] * n_overlaps > cap; then exactly the leading cap bytes are written and nothing beyond them.
+ * Results are integers or float64 sums in a fixed order: bit-identical from run to run, between host and device inputs and
+ * whichever table path a row took.  The taken-flags of a (row, overlap) are one bit per distinct v != 0: in LDS up to 2048 of them,
+ * in global scratch beyond.
+ * Host synchronisations: those of ai_label_tables on the same input, whose last one here brings the per-row results, and one more
+ * for the hit bytes (none when there are none): at most five.
+ */
+int ai_label_scores(ai_ctx* ctx, const int32_t* pred, const int32_t* gt, int32_t k, int64_t n, double threshold, int64_t min_points,
+                    int mem_kind, int32_t remove, const double* overlaps, int32_t n_overlaps, int64_t cap, uint8_t* hits,
+                    int64_t* hit_off, int32_t* row_counts, int32_t* tp, double* s_assoc);
+
+/*
  * The step that produces the chunks: chunk_and_downsample_point_clouds (pipeline/dataset/dataset_utils.py:489-567, called at
  * run_pipeline.py:129), per chunk and per cloud (non-ground / ground).  xyz and the index / point outputs are host or device
  * according to mem_kind; counts, offsets and stats are HOST values.  Indices are int32 (n < 2^30; box select: n < 2^31 - 256).

@@ -18,6 +18,14 @@ on (a)'s tables on its own, and (d) the bytes (a) must move -- (k + 1) * 4 * n r
 time they take at the box's copy rate (`ai_bench_copy`).  One JSON line, printed and written to `--out` (default
 profiles/score_map_line.json).  Kernel times come from a separate
 `rocprofv3 --kernel-trace --stats -- python tools/run_score.py --only-tables --reps 1 --out ""` run (profiles/score_map_kernels.txt).
+
+The score itself, on the same rows and alternating in the same way:
+  (e) `score_sweep(..., instance_level="device")`: the greedy matching and S_assoc on the device (`ai_label_scores`), AP on the host
+      from the hit flags;
+  (f) `score_sweep(..., instance_level="host")`: `label_tables`, then the instance-level arithmetic on dense tables on the host.
+(e) and (f) must give equal dicts.  Reported in a second JSON line (`--inst-out`, default profiles/score_inst_line.json): median and
+spread of both, the device call and the host finish of (e) on their own, and the host synchronisations of one call.  `--only-scores`
+runs (e) and (f) alone, `--only-device-scores` (e) alone -- for the kernel trace (profiles/score_inst_kernels.txt).
 """
 import argparse
 import ctypes as C
@@ -59,6 +67,10 @@ def main():
     ap.add_argument("--min-points", type=int, default=200)
     ap.add_argument("--only-tables", action="store_true", help="(a) alone: for a rocprofv3 kernel trace")
     ap.add_argument("--no-restated", action="store_true", help="skip (c), the NumPy restatement on one core")
+    ap.add_argument("--only-scores", action="store_true", help="(e) and (f) alone")
+    ap.add_argument("--only-device-scores", action="store_true", help="(e) alone: for a rocprofv3 kernel trace")
+    ap.add_argument("--inst-out", default=os.path.join(ROOT, "profiles", "score_inst_line.json"),
+                    help="file that receives the JSON line of (e) and (f) ('' : none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "score_map_line.json"), help="file that receives the JSON line ('' : none)")
     args = ap.parse_args()
     import torch
@@ -110,6 +122,59 @@ def main():
         fn()
         sync()
         return time.perf_counter() - t0
+
+    def score_legs():
+        """(e) against (f); with --only-device-scores (e) alone."""
+        res = {}
+
+        def leg(level):
+            def run():
+                res[level] = labels_api.score_sweep(preds, gt_map, args.min_points, remove=True, threshold=args.threshold,
+                                                    instance_level=level, ctx=ctx)
+            return run
+        levels = ("device",) if args.only_device_scores else ("device", "host")
+        times = {level: [] for level in levels}
+        for level in levels:
+            timed(leg(level))
+        for _ in range(max(args.reps, 10) if len(levels) == 2 else args.reps):
+            for level in levels:
+                times[level].append(timed(leg(level)))
+        td, tf = [], []
+        for _ in range(max(args.reps, 10)):                                 # (e) in its two parts
+            rows = []
+
+            def call():
+                rows[:] = labels_api._device_scores(preds, gt_map, args.threshold, args.min_points, True, ctx)
+            td.append(timed(call))
+            t0 = time.perf_counter()
+            finished = [labels_api._score_from_hits(*row) for row in rows]
+            tf.append(time.perf_counter() - t0)
+        assert all(str(a) == str(b) for a, b in zip(finished, res["device"]))
+        med = statistics.median
+        # by the header's count, not measured: pass 1 synchronises once per table size a row needs, then the result (and the hit bytes)
+        largest = max(int(t[0].size) for t in labels_api.label_tables(preds, gt_map, threshold=args.threshold, min_points=args.min_points, ctx=ctx))
+        syncs = 2 + int(largest > 4096) + int(largest > 65536)
+        inst = {"tool": "run_score", "legs": "scores", "chunks": args.chunks, "rows": k, "points": n, "threshold": args.threshold,
+                "min_points": args.min_points, "device_ms": 1e3 * med(times["device"]),
+                "device_spread_ms": 1e3 * (max(times["device"]) - min(times["device"])),
+                "device_ms_all": [round(1e3 * t, 3) for t in times["device"]],
+                "device_call_ms": 1e3 * med(td), "host_finish_ms": 1e3 * med(tf), "host_finish_share": med(tf) / med(times["device"]),
+                "scored_labels_per_row": [s["n_pred"] for s in res["device"]], "ap_per_row": [round(s["ap"], 6) for s in res["device"]],
+                "pairs_in_largest_row": largest, "host_synchronisations_device": syncs + 1, "host_synchronisations_host": syncs}
+        if "host" in res:
+            equal = all(str(a) == str(b) for a, b in zip(res["device"], res["host"]))      # str: NaN equals NaN
+            assert equal, "(e) and (f) differ"
+            inst.update({"host_ms": 1e3 * med(times["host"]), "host_spread_ms": 1e3 * (max(times["host"]) - min(times["host"])),
+                         "host_ms_all": [round(1e3 * t, 3) for t in times["host"]], "equal": equal,
+                         "host_over_device": med(times["host"]) / med(times["device"]),
+                         "device_below_host": bool(med(times["device"]) < med(times["host"]))})
+        print(json.dumps(inst), flush=True)
+        if args.inst_out:
+            with open(args.inst_out, "w") as f:
+                f.write(json.dumps(inst) + "\n")
+    if args.only_scores or args.only_device_scores:
+        score_legs()
+        return
     timed(one_call)
     gbps = C.c_double(0.0)
     _ffi.check(lib.ai_bench_copy(ctx._h, 1 << 28, 10, C.byref(gbps)), "ai_bench_copy")
@@ -158,6 +223,8 @@ def main():
     if args.out:
         with open(args.out, "w") as f:
             f.write(json.dumps(line) + "\n")
+    if not args.only_tables:
+        score_legs()
 
 
 if __name__ == "__main__":
