@@ -27,6 +27,19 @@ struct FlowCsr {
 
 #define FK_PAR(tk) (((tk).w >> 1) & 1)
 
+// How a task of the frontier reaches its rows, columns and weights (the graph policy of the bodies in ai_ncut_shared.h): the
+// buffer of its segment's depth.
+struct FlowGraph {
+  const FlowCsr& G;
+  struct Rows {
+    const int2* __restrict__ rowse;
+    __device__ __forceinline__ int2 operator()(int row) const { return rowse[row]; }
+  };
+  __device__ __forceinline__ Rows rows(const Task& tk) const { return Rows{G.rowse[FK_PAR(tk)]}; }
+  __device__ __forceinline__ const int32_t* col(const Task& tk) const { return G.col[FK_PAR(tk)]; }
+  __device__ __forceinline__ const double* w(const Task& tk) const { return G.w[FK_PAR(tk)]; }
+};
+
 // What the host uploads per segment; the task lists of a launch are expanded from these records on the device
 // (a pool of 24 chunks has ~150 k fine tasks: 5 MB per re-listing if the host wrote them).
 struct __attribute__((aligned(16))) SegRec {
@@ -57,38 +70,7 @@ __global__ __launch_bounds__(AI_BLOCK) void fk_rowse_from_rowptr(const int32_t* 
 // ----------------------------------------------------------------------------- degrees, scaling (normalized_cut.py:38-47)
 __global__ __launch_bounds__(AI_BLOCK) void fk_degree(const Task* __restrict__ tasks, FlowCsr G, double* __restrict__ deg,
                                                       double* __restrict__ sinv, double* __restrict__ pvol) {
-  __shared__ double sm[AI_BLOCK / 64];
-  const Task tk = tasks[blockIdx.x];
-  const int2* __restrict__ rowse = G.rowse[FK_PAR(tk)];
-  const double* __restrict__ wraw = G.w[FK_PAR(tk)];
-  const int l = threadIdx.x & (AI_LPR - 1), r = threadIdx.x / AI_LPR;
-  double acc = 0.0;
-  for (int row = tk.x + r; row < tk.y; row += AI_BLOCK / AI_LPR) {
-    const int2 se = rowse[row];
-    const int p0 = se.x, p1 = se.y;
-    double s = 0.0;
-    {
-      double w[AI_ROW_PF];
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q) {
-        const int p = p0 + l + q * AI_LPR;
-        w[q] = (p < p1) ? wraw[p] : 0.0;
-      }
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q)
-        if (p0 + l + q * AI_LPR < p1) s += w[q];
-    }
-    for (int p = p0 + l + AI_ROW_PF * AI_LPR; p < p1; p += AI_LPR) s += wraw[p];
-    s = ai_group16_sum(s);
-    if (l == 0) {
-      const double d = s + 1.0;
-      deg[row] = d;
-      sinv[row] = 1.0 / sqrt(d);
-      acc += d;
-    }
-  }
-  const double tot = ai_block_sum(acc, sm);
-  if (threadIdx.x == 0) pvol[blockIdx.x] = tot;
+  degree_body(tasks[blockIdx.x], FlowGraph{G}, deg, sinv, pvol);
 }
 
 // one block per record i: out[i] = sum of the partials of its fine tasks in a fixed order
@@ -105,37 +87,7 @@ __global__ __launch_bounds__(AI_BLOCK) void fk_scale(const Task* __restrict__ ta
                                                      double* __restrict__ u1, const int32_t* __restrict__ gate, int nbin) {
   const Task tk = tasks[blockIdx.x];
   if (tk.z < nbin && gate[tk.z] != 1) return;  // a child of a cut that fell apart: it is split by components first
-  const int2* __restrict__ rowse = G.rowse[FK_PAR(tk)];
-  const int32_t* __restrict__ col = G.col[FK_PAR(tk)];
-  const double* __restrict__ wraw = G.w[FK_PAR(tk)];
-  const double v = vol[recs[tk.z].aux];
-  const int l = threadIdx.x & (AI_LPR - 1), r = threadIdx.x / AI_LPR;
-  for (int row = tk.x + r; row < tk.y; row += AI_BLOCK / AI_LPR) {
-    const int2 se = rowse[row];
-    const int p0 = se.x, p1 = se.y;
-    const double si = sinv[row];
-    {
-      int c[AI_ROW_PF];
-      double w[AI_ROW_PF], sj[AI_ROW_PF];
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q) {
-        const int p = p0 + l + q * AI_LPR;
-        const bool ok = p < p1;
-        c[q] = ok ? col[p] : -1;
-        w[q] = ok ? wraw[p] : 0.0;
-      }
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q) sj[q] = (c[q] >= 0) ? sinv[c[q]] : 0.0;
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q)
-        if (c[q] >= 0) wm[p0 + l + q * AI_LPR] = (si * w[q]) * sj[q];
-    }
-    for (int p = p0 + l + AI_ROW_PF * AI_LPR; p < p1; p += AI_LPR) wm[p] = (si * wraw[p]) * sinv[col[p]];
-    if (l == 0) {
-      sinv2[row] = si * si;
-      u1[row] = sqrt(deg[row] / v);
-    }
-  }
+  scale_body(tk, FlowGraph{G}, vol[recs[tk.z].aux], deg, sinv, wm, sinv2, u1);
 }
 
 // ----------------------------------------------------------------------------- connected components (labels = positions)
@@ -1634,45 +1586,8 @@ __global__ __launch_bounds__(AI_BLOCK) void fk_resid_final(const SegRec* __restr
 // ----------------------------------------------------------------------------- harvest: threshold sweep (normalized_cut.py:13-34)
 __global__ __launch_bounds__(AI_BLOCK) void fk_minmax(const Task* __restrict__ ctasks, FlowCsr G, const double* __restrict__ ev,
                                                       MinMaxPart* __restrict__ part) {
-  __shared__ MinMaxPart sm[AI_BLOCK / 64];
   const Task tk = ctasks[blockIdx.x];
-  const int32_t* __restrict__ orig = G.orig[FK_PAR(tk)];
-  MinMaxPart r;
-  r.mn = 1e300;
-  r.mx = -1e300;
-  r.sumsq = 0.0;
-  r.amax = -1.0;
-  r.amax_id = 0x7fffffff;
-  r.amax_neg = 0;
-  for (int row = tk.x + threadIdx.x; row < tk.y; row += AI_BLOCK) {
-    const double e = ev[row];
-    MinMaxPart q;
-    q.mn = e;
-    q.mx = e;
-    q.sumsq = e * e;
-    q.amax = fabs(e);
-    q.amax_id = orig[row];
-    q.amax_neg = e < 0.0;
-    mm_merge(r, q);
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    MinMaxPart q;
-    q.mn = __shfl_xor(r.mn, o, 64);
-    q.mx = __shfl_xor(r.mx, o, 64);
-    q.sumsq = __shfl_xor(r.sumsq, o, 64);
-    q.amax = __shfl_xor(r.amax, o, 64);
-    q.amax_id = __shfl_xor(r.amax_id, o, 64);
-    q.amax_neg = __shfl_xor(r.amax_neg, o, 64);
-    mm_merge(r, q);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) sm[w] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    MinMaxPart t = sm[0];
-    for (int i = 1; i < AI_BLOCK / 64; ++i) mm_merge(t, sm[i]);
-    part[blockIdx.x] = t;
-  }
+  minmax_body(tk, ev, G.orig[FK_PAR(tk)], part);
 }
 
 // per record i: scale, np.allclose test, the 10 thresholds
@@ -1680,92 +1595,14 @@ __global__ void fk_minmax_final(const SegRec* __restrict__ recs, const MinMaxPar
                                 int S, double* __restrict__ scale, int32_t* __restrict__ nosplit, double* __restrict__ thr) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= S) return;
-  const int s = i;
   const SegRec sr = recs[i];
-  MinMaxPart r = part[sr.coff];
-  for (int t = sr.coff + 1; t < sr.coff + FK_NC(sr); ++t) mm_merge(r, part[t]);
-  const double nrm = sqrt(r.sumsq);
-  double sc = (nrm > 0.0) ? 1.0 / nrm : 1.0;
-  if (r.amax_neg) sc = -sc;
-  const double mn = (sc > 0.0) ? r.mn * sc : r.mx * sc;
-  const double mx = (sc > 0.0) ? r.mx * sc : r.mn * sc;
-  scale[s] = sc;
-  nosplit[s] = mm_thresholds(mn, mx, thr + s * AI_NUM_CUTS);
+  minmax_final_body(part, sr.coff, sr.coff + FK_NC(sr), 0, i, scale, nosplit, thr);
 }
 
 __global__ __launch_bounds__(AI_BLOCK) void fk_sweep(const Task* __restrict__ ftasks, const int32_t* __restrict__ nosplit, FlowCsr G,
                                                      const double* __restrict__ deg, const uint8_t* __restrict__ bin,
                                                      double* __restrict__ part) {
-  __shared__ double scut[AI_NUM_CUTS][AI_BLOCK + 1];
-  __shared__ double sdeg[AI_FINE_ROWS];
-  __shared__ int sbin[AI_FINE_ROWS];
-  const Task tk = ftasks[blockIdx.x];
-  if (nosplit[tk.z]) return;
-  const int2* __restrict__ rowse = G.rowse[FK_PAR(tk)];
-  const int32_t* __restrict__ col = G.col[FK_PAR(tk)];
-  const double* __restrict__ wraw = G.w[FK_PAR(tk)];
-  const int l = threadIdx.x & (AI_LPR - 1), r = threadIdx.x / AI_LPR;
-  if (threadIdx.x < AI_FINE_ROWS) {
-    const int row = tk.x + threadIdx.x;
-    sbin[threadIdx.x] = (row < tk.y) ? (int)bin[row] : -1;
-    sdeg[threadIdx.x] = (row < tk.y) ? deg[row] : 0.0;
-  }
-  double cut[AI_NUM_CUTS];
-#pragma unroll
-  for (int k = 0; k < AI_NUM_CUTS; ++k) cut[k] = 0.0;
-  for (int row = tk.x + r; row < tk.y; row += AI_BLOCK / AI_LPR) {
-    const int bi = bin[row];
-    const int2 se = rowse[row];
-    const int p0 = se.x, p1 = se.y;
-    {
-      int c[AI_ROW_PF], bj[AI_ROW_PF];
-      double w[AI_ROW_PF];
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q) {
-        const int p = p0 + l + q * AI_LPR;
-        const bool ok = p < p1;
-        c[q] = ok ? col[p] : -1;
-        w[q] = ok ? wraw[p] : 0.0;
-      }
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q) bj[q] = (c[q] >= 0) ? (int)bin[c[q]] : 0;
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q)
-        if (c[q] >= 0) {
-#pragma unroll
-          for (int k = 0; k < AI_NUM_CUTS; ++k) cut[k] += (k >= bj[q] && k < bi) ? w[q] : 0.0;
-        }
-    }
-    for (int p = p0 + l + AI_ROW_PF * AI_LPR; p < p1; p += AI_LPR) {
-      const int bj = bin[col[p]];
-      const double w = wraw[p];
-#pragma unroll
-      for (int k = 0; k < AI_NUM_CUTS; ++k) cut[k] += (k >= bj && k < bi) ? w : 0.0;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < AI_NUM_CUTS; ++k) scut[k][threadIdx.x] = cut[k];
-  __syncthreads();
-  double* out = part + (size_t)blockIdx.x * AI_SWEEP_VALS;
-  const int w = threadIdx.x >> 6, ln = threadIdx.x & 63;
-  for (int k = w; k < AI_NUM_CUTS; k += AI_BLOCK / 64) {
-    double a = 0.0;
-#pragma unroll
-    for (int q = 0; q < AI_BLOCK / 64; ++q) a += scut[k][ln + 64 * q];
-    a = ai_wave_sum(a);
-    if (ln == 0) out[k] = a;
-  }
-  if (threadIdx.x < 3 * AI_NUM_CUTS) {
-    const int which = threadIdx.x / AI_NUM_CUTS, k = threadIdx.x % AI_NUM_CUTS;
-    double a = 0.0;
-    for (int i = 0; i < AI_FINE_ROWS; ++i) {
-      const int bi = sbin[i];
-      if (bi < 0) break;
-      const bool inA = k < bi;
-      a += (which == 0) ? (inA ? sdeg[i] : 0.0) : (which == 1) ? (inA ? 0.0 : sdeg[i]) : (inA ? 1.0 : 0.0);
-    }
-    out[(which + 1) * AI_NUM_CUTS + k] = a;
-  }
+  sweep_body(ftasks, nosplit, FlowGraph{G}, deg, bin, part);
 }
 
 // per record i: the 10 costs, first strictly smaller wins, split iff mcut < T (res_*: what the host reads back; res_costs[i][10]:
@@ -1775,11 +1612,9 @@ __global__ __launch_bounds__(AI_BLOCK) void fk_sweep_final(const SegRec* __restr
                                                            int32_t* __restrict__ kstar,
                                                            int32_t* __restrict__ res_split, int32_t* __restrict__ res_ntrue,
                                                            double* __restrict__ res_mcut, double* __restrict__ res_costs) {
-  __shared__ double acc[SWF_STRIPES][AI_SWEEP_VALS];
   const int i = blockIdx.x;
-  const int s = i;
+  const int s = i;  // the record's index is its slot in the per-segment tables
   const SegRec sr = recs[i];
-  const int ft0 = sr.foff, ft1 = sr.foff + FK_NF(sr);
   if (nosplit[s]) {
     if (threadIdx.x == 0) {
       kstar[s] = 0;
@@ -1791,37 +1626,7 @@ __global__ __launch_bounds__(AI_BLOCK) void fk_sweep_final(const SegRec* __restr
     }
     return;
   }
-  const int c = threadIdx.x % AI_SWEEP_VALS, stripe = threadIdx.x / AI_SWEEP_VALS;
-  if (stripe < SWF_STRIPES) {
-    double a = 0.0;
-    for (int t = ft0 + stripe; t < ft1; t += SWF_STRIPES) a += part[(size_t)t * AI_SWEEP_VALS + c];
-    acc[stripe][c] = a;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double best = INFINITY;
-    int kb = 0;
-    double nb = 0.0;
-    for (int k = 0; k < AI_NUM_CUTS; ++k) {
-      double v[4];
-      for (int q = 0; q < 4; ++q) {
-        double a = 0.0;
-        for (int st = 0; st < SWF_STRIPES; ++st) a += acc[st][q * AI_NUM_CUTS + k];
-        v[q] = a;
-      }
-      const double cost = __dadd_rn(__ddiv_rn(v[0], v[1]), __ddiv_rn(v[0], v[2]));
-      if (res_costs) res_costs[i * AI_NUM_CUTS + k] = cost;
-      if (cost < best) {
-        best = cost;
-        kb = k;
-        nb = v[3];
-      }
-    }
-    kstar[s] = kb;
-    res_split[i] = (best < T) ? 1 : 0;
-    res_ntrue[i] = (int32_t)nb;
-    res_mcut[i] = best;
-  }
+  sweep_final_body(part, sr.foff, sr.foff + FK_NF(sr), T, s, res_costs, kstar, res_split, res_ntrue, res_mcut);
 }
 
 // ----------------------------------------------------------------------------- harvest: partition + rebuild, in place
@@ -2036,18 +1841,5 @@ __global__ __launch_bounds__(AI_BLOCK) void fk_rebuild_fill(const Task* __restri
 __global__ __launch_bounds__(AI_BLOCK) void fk_bin(const Task* __restrict__ ctasks, const int32_t* __restrict__ nosplit,
                                                    const double* __restrict__ scale, const double* __restrict__ thr,
                                                    const double* __restrict__ ev, uint8_t* __restrict__ bin) {
-  const Task tk = ctasks[blockIdx.x];
-  const int s = tk.z;
-  if (nosplit[s]) return;
-  const double sc = scale[s];
-  double th[AI_NUM_CUTS];
-#pragma unroll
-  for (int k = 0; k < AI_NUM_CUTS; ++k) th[k] = thr[s * AI_NUM_CUTS + k];
-  for (int row = tk.x + threadIdx.x; row < tk.y; row += AI_BLOCK) {
-    const double e = ev[row] * sc;
-    int b = 0;
-#pragma unroll
-    for (int k = 0; k < AI_NUM_CUTS; ++k) b += (e > th[k]) ? 1 : 0;
-    bin[row] = (uint8_t)b;
-  }
+  bin_body(ctasks, nosplit, scale, thr, ev, bin);
 }

@@ -7,41 +7,27 @@
 // For coarse tasks: the segment's fine-task range [x, y) and coarse-task range [z, w).
 typedef int4 TaskRange;
 
+// How a task of the Solver reaches its rows, columns and weights (the graph policy of the bodies in ai_ncut_shared.h): one CSR
+// for every task of a level.
+struct CsrGraph {
+  const int32_t* __restrict__ rowptr;
+  const int32_t* __restrict__ colp;
+  const double* __restrict__ wp;
+  struct Rows {
+    const int32_t* __restrict__ rowptr;
+    __device__ __forceinline__ int2 operator()(int row) const { return make_int2(rowptr[row], rowptr[row + 1]); }
+  };
+  __device__ __forceinline__ Rows rows(const Task&) const { return Rows{rowptr}; }
+  __device__ __forceinline__ const int32_t* col(const Task&) const { return colp; }
+  __device__ __forceinline__ const double* w(const Task&) const { return wp; }
+};
+
 // ----------------------------------------------------------------------------- degrees, scaling
 // deg_i = 1 + sum_j w_ij (W = w + I, normalized_cut.py:38,42); s_i = 1 / sqrt(deg_i) (:43)
 __global__ __launch_bounds__(AI_BLOCK) void k_degree(const Task* __restrict__ tasks, const int32_t* __restrict__ rowptr,
                                                      const double* __restrict__ wraw, double* __restrict__ deg,
                                                      double* __restrict__ sinv, double* __restrict__ pvol) {
-  __shared__ double sm[AI_BLOCK / 64];
-  const Task tk = tasks[blockIdx.x];
-  const int l = threadIdx.x & (AI_LPR - 1), r = threadIdx.x / AI_LPR;
-  double acc = 0.0;
-  for (int row = tk.x + r; row < tk.y; row += AI_BLOCK / AI_LPR) {
-    const int p0 = rowptr[row], p1 = rowptr[row + 1];
-    double s = 0.0;
-    {
-      // the first AI_ROW_PF rounds of a row (64 entries: nearly every row) are loaded together, then added in order
-      double w[AI_ROW_PF];
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q) {
-        const int p = p0 + l + q * AI_LPR;
-        w[q] = (p < p1) ? wraw[p] : 0.0;
-      }
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q)
-        if (p0 + l + q * AI_LPR < p1) s += w[q];
-    }
-    for (int p = p0 + l + AI_ROW_PF * AI_LPR; p < p1; p += AI_LPR) s += wraw[p];
-    s = ai_group16_sum(s);
-    if (l == 0) {
-      const double d = s + 1.0;
-      deg[row] = d;
-      sinv[row] = 1.0 / sqrt(d);
-      acc += d;
-    }
-  }
-  const double tot = ai_block_sum(acc, sm);
-  if (threadIdx.x == 0) pvol[blockIdx.x] = tot;
+  degree_body(tasks[blockIdx.x], CsrGraph{rowptr, nullptr, wraw}, deg, sinv, pvol);
 }
 
 // one block per segment: out[s] = sum of part[task0[s] .. task0[s+1]) in a fixed order
@@ -61,33 +47,7 @@ __global__ __launch_bounds__(AI_BLOCK) void k_scale(const Task* __restrict__ tas
                                                     const double* __restrict__ vol, double* __restrict__ wm,
                                                     double* __restrict__ sinv2, double* __restrict__ u1) {
   const Task tk = tasks[blockIdx.x];
-  const double v = vol[tk.z];
-  const int l = threadIdx.x & (AI_LPR - 1), r = threadIdx.x / AI_LPR;
-  for (int row = tk.x + r; row < tk.y; row += AI_BLOCK / AI_LPR) {
-    const int p0 = rowptr[row], p1 = rowptr[row + 1];
-    const double si = sinv[row];
-    {
-      int c[AI_ROW_PF];
-      double w[AI_ROW_PF], sj[AI_ROW_PF];
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q) {
-        const int p = p0 + l + q * AI_LPR;
-        const bool ok = p < p1;
-        c[q] = ok ? col[p] : -1;
-        w[q] = ok ? wraw[p] : 0.0;
-      }
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q) sj[q] = (c[q] >= 0) ? sinv[c[q]] : 0.0;
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q)
-        if (c[q] >= 0) wm[p0 + l + q * AI_LPR] = (si * w[q]) * sj[q];
-    }
-    for (int p = p0 + l + AI_ROW_PF * AI_LPR; p < p1; p += AI_LPR) wm[p] = (si * wraw[p]) * sinv[col[p]];
-    if (l == 0) {
-      sinv2[row] = si * si;
-      u1[row] = sqrt(deg[row] / v);
-    }
-  }
+  scale_body(tk, CsrGraph{rowptr, col, wraw}, vol[tk.z], deg, sinv, wm, sinv2, u1);
 }
 
 // ----------------------------------------------------------------------------- connected components
@@ -1001,50 +961,12 @@ __global__ __launch_bounds__(AI_BLOCK) void k_ritz_multi(const Task* __restrict_
 __global__ __launch_bounds__(AI_BLOCK) void k_minmax(const Task* __restrict__ ctasks, const int32_t* __restrict__ mode,
                                                      const double* __restrict__ ev, const int32_t* __restrict__ orig,
                                                      MinMaxPart* __restrict__ part) {
-  __shared__ MinMaxPart sm[AI_BLOCK / 64];
   const Task tk = ctasks[blockIdx.x];
   if (mode && mode[tk.z] != 0) return;  // a disconnected segment has no eigenvector: it is split by components
-  MinMaxPart r;
-  r.mn = 1e300;
-  r.mx = -1e300;
-  r.sumsq = 0.0;
-  r.amax = -1.0;
-  r.amax_id = 0x7fffffff;
-  r.amax_neg = 0;
-  for (int row = tk.x + threadIdx.x; row < tk.y; row += AI_BLOCK) {
-    const double e = ev[row];
-    MinMaxPart q;
-    q.mn = e;
-    q.mx = e;
-    q.sumsq = e * e;
-    q.amax = fabs(e);
-    q.amax_id = orig[row];
-    q.amax_neg = e < 0.0;
-    mm_merge(r, q);
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    MinMaxPart q;
-    q.mn = __shfl_xor(r.mn, o, 64);
-    q.mx = __shfl_xor(r.mx, o, 64);
-    q.sumsq = __shfl_xor(r.sumsq, o, 64);
-    q.amax = __shfl_xor(r.amax, o, 64);
-    q.amax_id = __shfl_xor(r.amax_id, o, 64);
-    q.amax_neg = __shfl_xor(r.amax_neg, o, 64);
-    mm_merge(r, q);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) sm[w] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    MinMaxPart t = sm[0];
-    for (int i = 1; i < AI_BLOCK / 64; ++i) mm_merge(t, sm[i]);
-    part[blockIdx.x] = t;
-  }
+  minmax_body(tk, ev, orig, part);
 }
 
-// Per segment: unit norm + sign convention folded into one scale; np.allclose(mn, mx) test
-// (normalized_cut.py:22); thresholds t_k = k * step + mn, step = (mx - mn) / 10, exactly as
-// np.linspace(mn, mx, 10, endpoint=False) computes them (:28).
+// Per segment: scale, np.allclose test and the 10 thresholds (minmax_final_body)
 __global__ void k_minmax_final(const int32_t* __restrict__ ctask0, const int32_t* __restrict__ mode,
                                const MinMaxPart* __restrict__ part, int S, int raw, double* __restrict__ scale,
                                int32_t* __restrict__ nosplit, double* __restrict__ thr) {
@@ -1055,127 +977,29 @@ __global__ void k_minmax_final(const int32_t* __restrict__ ctask0, const int32_t
     nosplit[s] = 1;
     return;
   }
-  MinMaxPart r = part[ctask0[s]];
-  for (int t = ctask0[s] + 1; t < ctask0[s + 1]; ++t) mm_merge(r, part[t]);
-  double sc = 1.0;
-  if (!raw) {
-    const double nrm = sqrt(r.sumsq);
-    sc = (nrm > 0.0) ? 1.0 / nrm : 1.0;
-    if (r.amax_neg) sc = -sc;
-  }
-  const double mn = (sc > 0.0) ? r.mn * sc : r.mx * sc;
-  const double mx = (sc > 0.0) ? r.mx * sc : r.mn * sc;
-  scale[s] = sc;
-  nosplit[s] = mm_thresholds(mn, mx, thr + s * AI_NUM_CUTS);
+  minmax_final_body(part, ctask0[s], ctask0[s + 1], raw, s, scale, nosplit, thr);
 }
 
 // bin_i = number of thresholds strictly below ev_i: mask_k(i) = (ev_i > t_k) = (k < bin_i)
 __global__ __launch_bounds__(AI_BLOCK) void k_bin(const Task* __restrict__ ctasks, const int32_t* __restrict__ nosplit,
                                                   const double* __restrict__ scale, const double* __restrict__ thr,
                                                   const double* __restrict__ ev, uint8_t* __restrict__ bin) {
-  const Task tk = ctasks[blockIdx.x];
-  const int s = tk.z;
-  if (nosplit[s]) return;  // no threshold will be applied to this segment (k_split_flags looks at split[] first)
-  const double sc = scale[s];
-  double th[AI_NUM_CUTS];
-#pragma unroll
-  for (int k = 0; k < AI_NUM_CUTS; ++k) th[k] = thr[s * AI_NUM_CUTS + k];
-  for (int row = tk.x + threadIdx.x; row < tk.y; row += AI_BLOCK) {
-    const double e = ev[row] * sc;
-    int b = 0;
-#pragma unroll
-    for (int k = 0; k < AI_NUM_CUTS; ++k) b += (e > th[k]) ? 1 : 0;
-    bin[row] = (uint8_t)b;
-  }
+  bin_body(ctasks, nosplit, scale, thr, ev, bin);
 }
 
-// All 10 cut costs in one pass over the edges (normalized_cut.py:4-11 for each threshold):
-//   cut_k    = sum over stored (i, j) with i in A_k, j in B_k of w_ij   (= (sum W - W_AA - W_BB) / 2)
-//   assocA_k = sum_{i in A_k} deg_i, assocB_k = sum_{i in B_k} deg_i   (deg of W = w + I)
-// An entry (i, j) with bin_j < bin_i is cut for every k in [bin_j, bin_i).
+// All 10 cut costs in one pass over the edges (sweep_body)
 __global__ __launch_bounds__(AI_BLOCK) void k_sweep(const Task* __restrict__ ftasks, const int32_t* __restrict__ nosplit,
                                                     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                     const double* __restrict__ wraw, const double* __restrict__ deg,
                                                     const uint8_t* __restrict__ bin, double* __restrict__ part) {
-  // the block's partial cut sums go through LDS transposed, so that each of the 10 columns is
-  // reduced by ONE wave (fixed order) instead of 40 block-wide reductions with two barriers each
-  __shared__ double scut[AI_NUM_CUTS][AI_BLOCK + 1];
-  __shared__ double sdeg[AI_FINE_ROWS];
-  __shared__ int sbin[AI_FINE_ROWS];
-  const Task tk = ftasks[blockIdx.x];
-  if (nosplit[tk.z]) return;
-  const int l = threadIdx.x & (AI_LPR - 1), r = threadIdx.x / AI_LPR;
-  if (threadIdx.x < AI_FINE_ROWS) {
-    const int row = tk.x + threadIdx.x;
-    sbin[threadIdx.x] = (row < tk.y) ? (int)bin[row] : -1;
-    sdeg[threadIdx.x] = (row < tk.y) ? deg[row] : 0.0;
-  }
-  double cut[AI_NUM_CUTS];
-#pragma unroll
-  for (int k = 0; k < AI_NUM_CUTS; ++k) cut[k] = 0.0;
-  for (int row = tk.x + r; row < tk.y; row += AI_BLOCK / AI_LPR) {
-    const int bi = bin[row];
-    const int p0 = rowptr[row], p1 = rowptr[row + 1];
-    {
-      int c[AI_ROW_PF], bj[AI_ROW_PF];
-      double w[AI_ROW_PF];
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q) {
-        const int p = p0 + l + q * AI_LPR;
-        const bool ok = p < p1;
-        c[q] = ok ? col[p] : -1;
-        w[q] = ok ? wraw[p] : 0.0;
-      }
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q) bj[q] = (c[q] >= 0) ? (int)bin[c[q]] : 0;
-#pragma unroll
-      for (int q = 0; q < AI_ROW_PF; ++q)
-        if (c[q] >= 0) {
-#pragma unroll
-          for (int k = 0; k < AI_NUM_CUTS; ++k) cut[k] += (k >= bj[q] && k < bi) ? w[q] : 0.0;
-        }
-    }
-    for (int p = p0 + l + AI_ROW_PF * AI_LPR; p < p1; p += AI_LPR) {
-      const int bj = bin[col[p]];
-      const double w = wraw[p];
-#pragma unroll
-      for (int k = 0; k < AI_NUM_CUTS; ++k) cut[k] += (k >= bj && k < bi) ? w : 0.0;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < AI_NUM_CUTS; ++k) scut[k][threadIdx.x] = cut[k];
-  __syncthreads();
-  double* out = part + (size_t)blockIdx.x * AI_SWEEP_VALS;
-  const int w = threadIdx.x >> 6, ln = threadIdx.x & 63;
-  for (int k = w; k < AI_NUM_CUTS; k += AI_BLOCK / 64) {
-    double a = 0.0;
-#pragma unroll
-    for (int q = 0; q < AI_BLOCK / 64; ++q) a += scut[k][ln + 64 * q];
-    a = ai_wave_sum(a);
-    if (ln == 0) out[k] = a;
-  }
-  // assocA_k / assocB_k / |A_k| over the task's rows in row order (30 threads, 32 rows each)
-  if (threadIdx.x < 3 * AI_NUM_CUTS) {
-    const int which = threadIdx.x / AI_NUM_CUTS, k = threadIdx.x % AI_NUM_CUTS;
-    double a = 0.0;
-    for (int i = 0; i < AI_FINE_ROWS; ++i) {
-      const int bi = sbin[i];
-      if (bi < 0) break;
-      const bool inA = k < bi;
-      a += (which == 0) ? (inA ? sdeg[i] : 0.0) : (which == 1) ? (inA ? 0.0 : sdeg[i]) : (inA ? 1.0 : 0.0);
-    }
-    out[(which + 1) * AI_NUM_CUTS + k] = a;
-  }
+  sweep_body(ftasks, nosplit, CsrGraph{rowptr, col, wraw}, deg, bin, part);
 }
 
-// Per segment: ncut_k = cut_k / assocA_k + cut_k / assocB_k; first strictly smaller cost wins
-// (normalized_cut.py:29-32); split iff mcut < T (:56).  One block per segment: column c of the
-// 40 partial columns is summed by 6 threads over interleaved task stripes, then in stripe order.
+// Per segment: the 10 costs, the winning threshold, split iff mcut < T (sweep_final_body); one block per segment
 __global__ __launch_bounds__(AI_BLOCK) void k_sweep_final(const int32_t* __restrict__ ftask0, const int32_t* __restrict__ nosplit,
                                                           const double* __restrict__ part, double T, double* __restrict__ costs,
                                                           int32_t* __restrict__ kstar, int32_t* __restrict__ split,
                                                           int32_t* __restrict__ ntrue, double* __restrict__ mcut_out) {
-  __shared__ double acc[SWF_STRIPES][AI_SWEEP_VALS];
   const int s = blockIdx.x;
   if (nosplit[s]) {
     if (threadIdx.x == 0) {
@@ -1187,37 +1011,8 @@ __global__ __launch_bounds__(AI_BLOCK) void k_sweep_final(const int32_t* __restr
     if (threadIdx.x < AI_NUM_CUTS) costs[s * AI_NUM_CUTS + threadIdx.x] = NAN;
     return;
   }
-  const int c = threadIdx.x % AI_SWEEP_VALS, stripe = threadIdx.x / AI_SWEEP_VALS;
-  if (stripe < SWF_STRIPES) {
-    double a = 0.0;
-    for (int t = ftask0[s] + stripe; t < ftask0[s + 1]; t += SWF_STRIPES) a += part[(size_t)t * AI_SWEEP_VALS + c];
-    acc[stripe][c] = a;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double best = INFINITY;
-    int kb = 0;
-    double nb = 0.0;
-    for (int k = 0; k < AI_NUM_CUTS; ++k) {
-      double v[4];
-      for (int q = 0; q < 4; ++q) {
-        double a = 0.0;
-        for (int st = 0; st < SWF_STRIPES; ++st) a += acc[st][q * AI_NUM_CUTS + k];
-        v[q] = a;
-      }
-      const double cost = __dadd_rn(__ddiv_rn(v[0], v[1]), __ddiv_rn(v[0], v[2]));
-      costs[s * AI_NUM_CUTS + k] = cost;
-      if (cost < best) {
-        best = cost;
-        kb = k;
-        nb = v[3];
-      }
-    }
-    kstar[s] = kb;
-    mcut_out[s] = best;
-    split[s] = (best < T) ? 1 : 0;
-    ntrue[s] = (int32_t)nb;
-  }
+  __builtin_assume(costs != nullptr);  // the Solver always wants them; with the body's test left in, this kernel takes 240 VGPRs for 90
+  sweep_final_body(part, ftask0[s], ftask0[s + 1], T, s, costs, kstar, split, ntrue, mcut_out);
 }
 
 // ----------------------------------------------------------------------------- partition + rebuild

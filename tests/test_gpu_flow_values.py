@@ -117,6 +117,28 @@ def test_root_of_a_connected_golden_matches_the_imported_reference(dumps, name):
     assert np.abs(r["costs"][~big] - ref[~big]).max(initial=0.0) <= 1e-9
 
 
+@pytest.mark.parametrize("name", CONNECTED)
+def test_the_solver_sweeps_the_root_vector_of_the_frontier_to_the_same_bits(dumps, name):
+    """The contract of csrc/ai_ncut_shared.h across the two solvers: the level-synchronous Solver (ai_sweep: k_minmax .. k_sweep_final)
+    given the frontier's own root vector ev * scale forms the frontier's ten costs, its mcut and its mask (fk_minmax ..
+    fk_sweep_final) bit for bit.  The root's rows are in caller order in both, so tasks and stripes hold the same rows."""
+    import flow_cases
+    from autoinst_amd import ncuts_api as api
+    recs = load(dumps, name)[0]
+    graphs = flow_cases.build(name)[0]
+    n = graphs[0].n
+    root = [r for r in recs if r["n"] == n]
+    assert len(root) == 1 and root[0]["kind"] == "L" and not root[0]["nosplit"]
+    r = root[0]
+    o = np.argsort(r["ids"])          # back to original order
+    e = (r["ev"] * r["scale"])[o]
+    costs, mask, mcut = api.sweep(graphs[0], e)
+    graphs[0].free()
+    assert costs.tobytes() == r["costs"].tobytes(), (costs, r["costs"])
+    assert np.float64(mcut).tobytes() == np.float64(r["mcut"]).tobytes()
+    assert np.array_equal(mask, e > r["thr"][r["kstar"]])     # bin > kstar: the thresholds strictly below e number more than kstar
+
+
 def test_batch_equals_solo_bit_for_bit_per_segment(dumps):
     """ai_ncut_batch promises the results of separate ai_ncut calls: per segment m, theta, ev, scale, thr, costs and kstar are
     byte-equal to the solo call's, in one pool and with a window that serialises admission."""

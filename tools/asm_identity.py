@@ -8,7 +8,7 @@ must come out with 0 different.
     python tools/asm_identity.py [--rename OLD=NEW ...] OLD.s[,OLD2.s...] NEW.s[,NEW2.s...]
 
 Lines: DIFF (exit status 1), SWAP (same length, same mnemonics, the only differing lines have the two source operands of a commutative
-instruction exchanged: the same bits; counted per mnemonic, exit status 0), ONLY-OLD / ONLY-NEW for a kernel of the project's
+instruction exchanged: the same bits; counted per mnemonic, exit status 0), under a DIFF one line with the descriptor lines and the instruction counts per mnemonic that differ, ONLY-OLD / ONLY-NEW for a kernel of the project's
 anonymous namespace that one side lacks.  `--rename OLD=NEW` (names as these lines print them) compares a kernel that the old side
 calls OLD with the one the new side calls NEW."""
 import re, sys, subprocess
@@ -64,6 +64,23 @@ def swaps(vo, vn):
         count[ma] = count.get(ma, 0) + 1
     return count
 
+def resources(vo, vn):
+    """What a DIFF kernel kept: the `.amdhsa_*` descriptor lines (registers, LDS, scratch, accum_offset) and the per-mnemonic
+    instruction counts that differ, old -> new; vector and memory mnemonics (v_*, ds_*, global/flat/buffer/scratch_*, s_load*) first."""
+    def split(v):
+        desc = {l.split(' ')[0]: l.partition(' ')[2] for l in v if l.startswith('.amdhsa_')}
+        count = {}
+        for l in v:
+            if not l.startswith('.') and not l.endswith(':'):
+                count[l.split(' ')[0]] = count.get(l.split(' ')[0], 0) + 1
+        return desc, count
+    (do, co), (dn, cn) = split(vo), split(vn)
+    heavy = lambda m: bool(re.match(r'(v_|ds_|global_|flat_|buffer_|scratch_|s_load|s_buffer_load)', m))
+    show = lambda o, n, keys: ' '.join('%s:%s->%s' % (k, o.get(k, 0), n.get(k, 0)) for k in keys) or 'equal'
+    moved = sorted(k for k in set(co) | set(cn) if co.get(k, 0) != cn.get(k, 0))
+    return 'descriptor %s | vector+memory %s | other %s' % (show(do, dn, sorted(k for k in set(do) | set(dn) if do.get(k) != dn.get(k))),
+                                                            show(co, cn, [k for k in moved if heavy(k)]), show(co, cn, [k for k in moved if not heavy(k)]))
+
 args, renames = sys.argv[1:], {}
 while args and args[0] == '--rename':
     o, _, n = args[1].partition('=')
@@ -106,6 +123,7 @@ for no, nn in pairs:
             else:
                 diff += 1
                 print('DIFF', label, po.split('/')[-1], pn.split('/')[-1], len(vo), len(vn))
+                print('    ' + resources(vo, vn))
 nk = sum(1 for no, nn in pairs if ours(nn))
 print('compared %d function pairs (%d project kernels by name): %d identical, %d operand swaps only, %d different'
       % (same + swapped + diff, nk, same, swapped, diff))
