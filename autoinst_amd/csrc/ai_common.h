@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/autoinst_hip.h"
+#include "ai_ncut_params.h"  // AI_FLOW_UPSLOTS
 
 // ----------------------------------------------------------------------------- errors
 void ai_set_error(const char* fmt, ...);
@@ -85,7 +86,6 @@ struct ArenaScope {
 #define AI_PINNED_INTS 4096
 #define AI_CHECK_DEPTH 16
 #define AI_STAGE_BYTES ((size_t)8 << 20)
-#define AI_FLOW_UPSLOTS 32                       // pinned upload ring of the asynchronous frontier (ai_flow.inc)
 #define AI_FLOW_EVENTS (AI_FLOW_UPSLOTS + 2)     // one event per upload slot + wave stage + main-stream mark
 // Device buffers of the graphs a context hands out (ai_csr): hipFree synchronises the whole device,
 // which with several host threads stalls every other thread's stream, so freed buffers are kept and

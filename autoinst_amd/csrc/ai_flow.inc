@@ -16,77 +16,20 @@
 // Every segment also carries the heights of the cut tree (FSeg::front / path; DESIGN.md section 21) and every group records the
 // height of the boundary in front of it and the cost of the cut it was refused: ai_ncut_tree returns them, ai_ncut drops them.
 
-struct RangeAlloc {  // first-fit allocator of index ranges (stable task indices)
-  std::map<int, int> fr;  // start -> length
-  void init(int cap) {
-    fr.clear();
-    fr[0] = cap;
-  }
-  int alloc(int n) {
-    for (auto it = fr.begin(); it != fr.end(); ++it)
-      if (it->second >= n) {
-        const int b = it->first, len = it->second;
-        fr.erase(it);
-        if (len > n) fr[b + n] = len - n;
-        return b;
-      }
-    return -1;
-  }
-  void release(int b, int n) {
-    auto it = fr.emplace(b, n).first;
-    auto nx = std::next(it);
-    if (nx != fr.end() && it->first + it->second == nx->first) {
-      it->second += nx->second;
-      fr.erase(nx);
-    }
-    if (it != fr.begin()) {
-      auto pv = std::prev(it);
-      if (pv->first + pv->second == it->first) {
-        pv->second += it->second;
-        fr.erase(it);
-      }
-    }
-  }
-};
+// The segment and group records (FSeg, FLeaf), the allocator of stable task indices (RangeAlloc), the map of the pinned host area with
+// the layouts of a wave's tables (WaveResults, HistRows, CoefTable) and the rules that turn a harvested segment into children and
+// groups (child_solve_again, children_of_cut, children_of_components) are host-only and live in ai_flow_host.h, where a CPU test
+// reaches them (tests/test_host_flow.py; DESIGN.md section 29).  This file holds no offset into the pinned area of its own.
 
-struct FSeg {  // host record of a live segment
-  int g0 = 0, n = 0, chunk = 0, par = 0;
-  int slot = -1;          // Lanczos state (pool segments only)
-  int t0 = 0, cap = 0;
-  int f0 = -1, c0 = -1;   // stable fine / coarse index ranges (pool segments only)
-  int m = 0;              // size of T at freeze
-  int aux = 0;            // index in the list the record was derived from
-  bool frozen = false;
-  bool binary_child = false;  // child of a Fiedler cut (or a root): its connectivity is not known yet
-  int vdelta = 0;             // slab row of position 0 of its chunk
-  int warm_n = 0;             // (warm start) rows of the last SOLVED ancestor, whose second Ritz vector lies at this segment's positions in warm[]; 0: none
-  int pca = 0;                // (principal-axis start) 1 + chunk while the segment is prepared without a solved ancestor and its graph kept its points; 0: not
-  int restarts = 0;           // times the segment was solved again because its Ritz pair failed the true-residual test
-  double prev_true = 0.0;     // the true residual that sent it back
-  // cut tree (ai_ncut_tree): the threshold at which the boundary in front of the segment's first position appears, and the largest
-  // cost among the cuts that produced the segment (a Fiedler cut costs its mcut, a split into components exactly 0); -inf at a root
-  double front = -INFINITY, path = -INFINITY;
+struct Rider {  // a small host table that rides along with a wave's records (Flow::expand): where it is, where it goes on the device, its bytes
+  const void* host = nullptr;
+  void* dev = nullptr;
+  size_t bytes = 0;
 };
-
-struct FLeaf {  // a group: where it starts, the height of the boundary in front of it, the mcut of the cut it was refused (NaN: never solved)
-  int32_t g0;
-  double front, cost;
-};
-
-static inline int fk_nf(int n) { return (n + AI_FINE_ROWS - 1) / AI_FINE_ROWS; }
-static inline int fk_nc(int n) { return (n + AI_COARSE_ROWS - 1) / AI_COARSE_ROWS; }
 
 class Flow {
  public:
   static constexpr int RING = 16;      // pool list versions kept alive (a relist waits for the checks that still read the entry it rewrites: with 4 entries it waited ~40 us on average, 18 ms of a 12-chunk call)
-  static constexpr size_t UPSLOT_BYTES = (size_t)256 << 10;
-  static constexpr size_t PIN_UP = AI_FLOW_UPSLOTS * UPSLOT_BYTES;  // 8 MB
-  static constexpr size_t STATUS_BYTES = (size_t)64 << 10;          // status[slot]: rows of T at which the device froze the slot's segment
-  static constexpr size_t PIN_STATUS = STATUS_BYTES;
-  static constexpr size_t PIN_RES = (size_t)1 << 20;
-  static constexpr size_t PIN_HIST = (size_t)16 << 20;
-  static constexpr size_t PIN_COEF = (size_t)8 << 20;
-  static constexpr size_t PIN_TOTAL = PIN_UP + PIN_STATUS + PIN_RES + PIN_HIST + PIN_COEF;
   static constexpr int TS_CAP = 1 << 16;  // launches whose device-clock stamps are kept
   static constexpr int AHEAD = 10;        // steps the host may launch past the last step the device has reported (it reports every 2nd)
   static constexpr int AHEAD_SMALL = 8;   // ... for a small pool: short steps, children should not wait long for the host's position (4 .. 12 measured: no difference beyond the run-to-run spread)
@@ -263,10 +206,13 @@ class Flow {
   }
   int pool_slot = 0;
   bool pool_slot_used[POOL_SLOTS] = {false};
-  char* pin_status() { return pin + PIN_UP; }
-  char* pin_res() { return pin + PIN_UP + PIN_STATUS; }
-  char* pin_hist() { return pin + PIN_UP + PIN_STATUS + PIN_RES; }
-  char* pin_coef() { return pin + PIN_UP + PIN_STATUS + PIN_RES + PIN_HIST; }
+  // the regions of the pinned area; what lies inside them is ai_flow_host.h's to say
+  char* pin_status() { return pin + PIN_OFF_STATUS; }
+  char* pin_res() { return pin + PIN_OFF_RES; }
+  char* pin_hist() { return pin + PIN_OFF_HIST; }
+  char* pin_coef() { return pin + PIN_OFF_COEF; }
+  double* hist_rows() { return (double*)pin_hist(); }   // HistRows(w_mp)
+  double* coef_host() { return (double*)pin_coef(); }   // CoefTable(nA, w_mp, warm)
 
   FlowLz lz() {
     FlowLz L;
@@ -292,7 +238,7 @@ class Flow {
       if (!ctx->fev[i]) AI_HIP(hipEventCreateWithFlags(&ctx->fev[i], hipEventDisableTiming));
     sw = ctx->wave;
     pin = ctx->fpin;
-    progress = (volatile int32_t*)(pin_res() + 32);  // layout of the result area: +0 component count, +32 progress, +64 .. PIN_RES/2 wave results, then the slab table
+    progress = res_progress(pin_res());
     *progress = 0;
     return AI_OK;
   }
@@ -319,7 +265,7 @@ class Flow {
       return AI_ERR_INTERNAL;
     }
     // the table only ever grows by appending: rewriting the pinned copy while an earlier upload is in flight is harmless
-    double** tab = (double**)(pin_res() + PIN_RES / 2);  // second half of the result area: the wave's results stay below
+    double** tab = res_slab_table(pin_res());  // second half of the result area: the wave's results stay below
     for (size_t i = 0; i < slabs.size(); ++i) tab[i] = slabs[i];
     AI_HIP(hipMemcpyAsync(d_slabtab.p, tab, slabs.size() * sizeof(double*), hipMemcpyHostToDevice, sm));
     slabtab_n = slabs.size();
@@ -491,7 +437,7 @@ class Flow {
     AI_TRY(w_nosplit.alloc((size_t)WCAP));
     AI_TRY(w_ncomp.alloc((size_t)WCAP));
     AI_TRY(ss_d.alloc((size_t)WCAP));
-    AI_TRY(coef_d.alloc(PIN_COEF / sizeof(double) + 4 * 512 + 64));
+    AI_TRY(coef_d.alloc(COEF_DEV_DOUBLES));
     if (clock_spmv) {
       AI_TRY(tstamps.alloc((size_t)2 * TS_CAP));
       AI_TRY(tblock.alloc((size_t)2 * (FLIST + 1)));
@@ -684,13 +630,12 @@ class Flow {
 
   // ------------------------------------------------------------------------------------------------- waves
   // records of `segs` -> pinned stage area -> (on the device) a kept copy + the task lists; up to two small host tables ride along
-  int expand(const std::vector<FSeg>& segs, DevBuf<SegRec>& drec, Task* fine, Task* coarse, int stable, int& nf, int& nc, const void* x0 = nullptr,
-             void* xd0 = nullptr, size_t xb0 = 0, const void* x1 = nullptr, void* xd1 = nullptr, size_t xb1 = 0) {
+  int expand(const std::vector<FSeg>& segs, DevBuf<SegRec>& drec, Task* fine, Task* coarse, int stable, int& nf, int& nc, Rider x0 = {}, Rider x1 = {}) {
     if (segs.empty()) {
       nf = nc = 0;
       return AI_OK;
     }
-    if ((int)segs.size() > WCAP || segs.size() * sizeof(int32_t) + 64 > PIN_RES / 2) {
+    if ((int)segs.size() > WCAP || !res_child_comps_fit(segs.size())) {
       ai_set_error("internal: %zu segments in one wave (capacity %d)", segs.size(), WCAP);
       return AI_ERR_INTERNAL;
     }
@@ -700,7 +645,7 @@ class Flow {
       ai_set_error("internal: wave task lists overflow (%d fine, %d coarse)", nf, nc);
       return AI_ERR_INTERNAL;
     }
-    const size_t r0 = (xb0 + 15) & ~(size_t)15, r1 = (xb1 + 15) & ~(size_t)15;
+    const size_t r0 = (x0.bytes + 15) & ~(size_t)15, r1 = (x1.bytes + 15) & ~(size_t)15;
     char* pr = wpin(recs.size() * sizeof(SegRec));
     char* p0 = r0 ? wpin(r0) : nullptr;
     char* p1 = r1 ? wpin(r1) : nullptr;
@@ -709,15 +654,25 @@ class Flow {
       return AI_ERR_INTERNAL;
     }
     memcpy(pr, recs.data(), recs.size() * sizeof(SegRec));
-    if (r0) memcpy(p0, x0, xb0);
-    if (r1) memcpy(p1, x1, xb1);
+    if (r0) memcpy(p0, x0.host, x0.bytes);
+    if (r1) memcpy(p1, x1.host, x1.bytes);
     hipLaunchKernelGGL(fk_expand_wave, dim3((unsigned)segs.size()), dim3(AI_BLOCK), 0, sw, (const SegRec*)pr, drec.p, fine, coarse, stable, (const int4*)p0,
-                       (int4*)xd0, (int)(r0 / 16), (const int4*)p1, (int4*)xd1, (int)(r1 / 16));
+                       (int4*)x0.dev, (int)(r0 / 16), (const int4*)p1, (int4*)x1.dev, (int)(r1 / 16));
     AI_KERNEL_CHECK();
     return AI_OK;
   }
 
   void leaf(int g0, double front, double cost) { leaves.push_back(FLeaf{g0, front, cost}); }
+
+  // A segment gives back what it holds of the pool: its stable task ranges at once, its Lanczos slot to `slots` -- free_slots where
+  // nothing on the device can name the slot any more, wslots_to_free for a harvested parent (checks launched before it left the
+  // lists may still name it: wave_finish frees those after children_prep has reaped them).  The record keeps its numbers: a parent
+  // that split is listed once more with them; who lets the segment wait clears them (FSeg::detach).
+  void give_back(const FSeg& s, std::vector<int>& slots) {
+    if (s.slot >= 0) slots.push_back(s.slot);
+    if (s.f0 >= 0) fa.release(s.f0, fk_nf(s.n));
+    if (s.c0 >= 0) ca.release(s.c0, fk_nc(s.n));
+  }
 
   // chunks whose last segment has become a group give their slab rows back; waiting chunks take them
   int retire_chunks() {
@@ -760,10 +715,10 @@ class Flow {
     wM.clear();
     // as many frozen segments as the pinned history / coefficient buffers take
     w_mp = 0;
-    while (!pend_solved.empty() && wA.size() < 512) {
+    while (!pend_solved.empty() && wA.size() < (size_t)WAVE_MAX_SEGS) {
       const int mp = std::max(w_mp, pend_solved.front().m);
       const size_t k = wA.size() + 1;
-      if (k * ((size_t)3 * mp + FK_HIST_HEAD) * sizeof(double) > PIN_HIST || ((warm ? 2 : 1) * k * (size_t)mp + 4 * k) * sizeof(double) > PIN_COEF) {
+      if (!wave_fits(k, (size_t)mp, warm != 0)) {
         if (wA.empty()) {
           ai_set_error("internal: one segment's T (%d rows) exceeds the pinned buffers", mp);
           return AI_ERR_INTERNAL;
@@ -793,7 +748,7 @@ class Flow {
     if (!wA.empty()) {
       stats.lanczos_solves += (int64_t)wA.size();
       hipLaunchKernelGGL(fk_pack_hist, dim3((unsigned)wA.size()), dim3(AI_BLOCK), 0, sw, (const SegRec*)wrecP.p, L, (const double*)s_theta.p,
-                         (const double*)s_resid.p, w_mp, (double*)pin_hist());  // straight into pinned host memory
+                         (const double*)s_resid.p, w_mp, hist_rows());  // straight into pinned host memory
       AI_KERNEL_CHECK();
     }
     if (!wM.empty()) {
@@ -807,7 +762,7 @@ class Flow {
       AI_KERNEL_CHECK();
       hipLaunchKernelGGL(fk_rootflag, dim3(w_ncM), dim3(AI_BLOCK), 0, sw, (const Task*)(coarseP.p + w_coffM), (const int32_t*)parent.p, rc.p, key.p);
       AI_KERNEL_CHECK();
-      AI_TRY(ai_exclusive_scan_i32(sw, rc.p + w_loM, ord.p + w_loM, len, scantmp.p, (int32_t*)pin_res()));  // the total straight into pinned memory
+      AI_TRY(ai_exclusive_scan_i32(sw, rc.p + w_loM, ord.p + w_loM, len, scantmp.p, res_comp_total(pin_res())));  // the total straight into pinned memory
     }
     if (wM.empty() && wA.empty()) return wave_s2();  // only new roots: nothing for the host to do in between (no coefficients either)
     AI_HIP(hipEventRecord(wave_ev(), sw));
@@ -834,16 +789,13 @@ class Flow {
   }
   // (helper thread) reads the packed histories in pinned memory, writes the packed upload {cu[nA], m[nA], coef[nA][mp]} and resid[nA]
   void ritz_job(size_t nA) {
-    double* pr_mcut = (double*)(pin_res() + 64 + (((size_t)3 * nA * sizeof(int32_t) + 15) & ~(size_t)15));
-    double* pr_resid = pr_mcut + nA;
-    const size_t pitch = (size_t)3 * w_mp + FK_HIST_HEAD;
-    const double* hp = (const double*)pin_hist();
-    double* h_cu = (double*)pin_coef();
-    double* h_th = h_cu + nA;
-    int32_t* h_m = (int32_t*)(h_cu + 2 * nA);
-    double* hc = h_cu + 3 * nA;
-    double* h_cu2 = hc + nA * (size_t)w_mp;          // (warm start) second Ritz vector: cu2[nA], coef2[nA][mp]
-    double* hc2 = h_cu2 + nA;
+    double* pr_resid = WaveResults(nA).resid(res_wave(pin_res()));
+    const HistRows H((size_t)w_mp);
+    const double* hp = hist_rows();
+    const CoefTable C(nA, (size_t)w_mp, warm != 0);
+    double* const ct = coef_host();
+    double *h_cu = C.cu(ct), *h_th = C.theta(ct), *h_cu2 = C.cu2(ct);   // (warm start) second Ritz vector: cu2[nA], coef2[nA][mp]
+    int32_t* h_m = C.m(ct);
     std::vector<double> sv, sv2;
     std::vector<std::vector<double>> prevv(1);
     const std::vector<int> cluster0{0};
@@ -851,38 +803,33 @@ class Flow {
     hist_bad = 0;
     for (size_t i = 0; i < nA; ++i) {
       const FSeg& s = wA[i];
-      const double* row = hp + i * pitch;
+      const double* row = H.row(hp, i);
       const int m = s.m;
       if (m <= 0 || m > w_mp) {
         ritz_err = m == 0 ? -1 : m;
         return;
       }
-      unsigned long long sum = 0, w;
-      auto bits = [](double v) { unsigned long long u; memcpy(&u, &v, sizeof u); return u; };
-      sum = bits(row[0]) + bits(row[1]) + (unsigned long long)(long long)m;
-      const double *a = row + FK_HIST_HEAD, *b = a + w_mp, *g = b + w_mp;
-      for (int j = 0; j < m; ++j) sum += bits(a[j]) + bits(b[j]) + bits(g[j]);
-      memcpy(&w, &row[3], sizeof w);
+      const bool sum_ok = H.sum_matches(row, m);
       const bool spoil = inject_hist >= 0 && n_harvested + (long long)i == inject_hist && hist_tries == 0;  // test hook
-      if (row[2] != (double)m || w != sum || spoil) {
+      if (!H.m_matches(row, m) || !sum_ok || spoil) {
         hist_bad = 1;
-        hist_bad_m_dev = row[2];
+        hist_bad_m_dev = H.m_dev(row);
         hist_bad_m_host = m;
         hist_bad_row = (int)i;
-        hist_bad_sum = (w != sum);
+        hist_bad_sum = !sum_ok;
         return;
       }
     }
     for (size_t i = 0; i < nA; ++i) {
       const FSeg& s = wA[i];
-      const double* row = hp + i * pitch;
-      const double h_theta = row[0], h_resid = row[1];
-      const double *a = row + FK_HIST_HEAD, *b = a + w_mp, *g = b + w_mp;
+      const double* row = H.row(hp, i);
+      const double h_theta = H.theta(row), h_resid = H.resid(row);
+      const double *a = H.a(row), *b = H.b(row), *g = H.g(row);
       const int m = s.m;
       double theta = 0.0;
       ai_tridiag_top(a, b, m, (h_theta > 0.0) ? &h_theta : nullptr, &theta, sv);
       double cu = 0.0;
-      double* c = hc + i * (size_t)w_mp;
+      double* c = C.coef(ct, i);
       for (int j = 0; j < m; ++j) {
         const double cj = sv[j] / b[j];  // v_j = (R_j - g_j u1) / b_j
         c[j] = cj;
@@ -894,7 +841,7 @@ class Flow {
         for (int j = 0; j < m / 2; ++j) std::swap(c[j], c[m - 1 - j]);
       }
       if (warm) {
-        double* c2 = hc2 + i * (size_t)w_mp;
+        double* c2 = C.coef2(ct, i);
         double cu2 = 0.0;
         if (m >= 2) {
           // The next Ritz vector(s) below the top one, cheaply: inverse iteration with a shift just below theta, kept orthogonal to
@@ -921,20 +868,18 @@ class Flow {
       pr_resid[i] = h_resid;
     }
     if (guard_log) {
-      hist_copy.assign(hp, hp + nA * pitch);
-      coef_copy.assign(h_cu, h_cu + 3 * nA + nA * (size_t)w_mp);
+      hist_copy.assign(hp, hp + H.doubles(nA));
+      coef_copy.assign(ct, ct + C.top_doubles());
     }
   }
   int wave_s2() {
     wpin_off = 0;
     const size_t nA = wA.size();
-    const double* cu_dev = coef_d.p;
-    const double* th_dev = coef_d.p + nA;
-    const int32_t* wm_dev = (const int32_t*)(coef_d.p + 2 * nA);
-    const double* coef_dev = coef_d.p + 3 * nA;
-    // results straight into pinned host memory: {split[nA], ntrue[nA], kstar[nA]}, mcut[nA], resid[nA]
-    int32_t* pr_i = (int32_t*)(pin_res() + 64);
-    double* pr_mcut = (double*)(pin_res() + 64 + (((size_t)3 * nA * sizeof(int32_t) + 15) & ~(size_t)15));
+    const CoefTable C(nA, (size_t)w_mp, warm != 0);
+    const double* const cd = coef_d.p;
+    // results straight into pinned host memory (WaveResults)
+    const WaveResults R(nA);
+    char* const rw = res_wave(pin_res());
     if (nA && hist_bad) {
       // a row of the packed histories arrived damaged (or the device froze a segment at another size of T than the host knows):
       // nothing of the wave has been used yet -- pack again and look again; three failures end the call
@@ -945,9 +890,10 @@ class Flow {
         if (FILE* f = fopen(guard_log, "a")) {
           fprintf(f, "HISTROW wave_rows %zu row %d mp %d %s device_m %.0f host_m %d attempt %d J %d g0 %d n %d\n", nA, hist_bad_row, w_mp, hist_bad_sum ? "checksum" : "size", hist_bad_m_dev,
                   hist_bad_m_host, hist_tries + 1, J, wA[hist_bad_row].g0, wA[hist_bad_row].n);
-          const double* row = (const double*)pin_hist() + (size_t)hist_bad_row * ((size_t)3 * w_mp + FK_HIST_HEAD);
+          const HistRows H((size_t)w_mp);
+          const double* row = H.row(hist_rows(), (size_t)hist_bad_row);
           fprintf(f, "head");
-          for (int j = 0; j < 20 && j < 3 * w_mp + FK_HIST_HEAD; ++j) fprintf(f, " %a", row[j]);
+          for (int j = 0; j < 20 && j < (int)H.pitch(); ++j) fprintf(f, " %a", row[j]);
           fprintf(f, "\n");
           fclose(f);
         }
@@ -959,7 +905,7 @@ class Flow {
       }
       const FlowLz L = lz();
       hipLaunchKernelGGL(fk_pack_hist, dim3((unsigned)nA), dim3(AI_BLOCK), 0, sw, (const SegRec*)wrecP.p, L, (const double*)s_theta.p, (const double*)s_resid.p, w_mp,
-                         (double*)pin_hist());
+                         hist_rows());
       AI_KERNEL_CHECK();
       AI_HIP(hipEventRecord(wave_ev(), sw));
       wstate = W_S1;
@@ -976,21 +922,18 @@ class Flow {
         return AI_ERR_INTERNAL;
       }
       n_harvested += (long long)nA;
-      const double* h_cu = (const double*)pin_coef();
-      AI_HIP(hipMemcpyAsync(coef_d.p, h_cu, (3 * nA + nA * (size_t)w_mp + (warm ? nA + nA * (size_t)w_mp : 0)) * sizeof(double), hipMemcpyHostToDevice, sw));
+      AI_HIP(hipMemcpyAsync(coef_d.p, coef_host(), C.bytes(), hipMemcpyHostToDevice, sw));
     }
     if (nA) {
-      const double* cu2_dev = coef_dev + nA * (size_t)w_mp;
-      const double* coef2_dev = cu2_dev + nA;
-      hipLaunchKernelGGL(fk_ritz, dim3(w_ncA), dim3(AI_BLOCK), 0, sw, (const Task*)coarseP.p, (const SegRec*)wrecP.p, wm_dev, coef_dev, w_mp, cu_dev,
-                         (const double*)u1.p, (double* const*)d_slabtab.p, (size_t)W, ev.p, warm ? coef2_dev : (const double*)nullptr,
-                         warm ? cu2_dev : (const double*)nullptr, warm ? ev2.p : (double*)nullptr);
+      hipLaunchKernelGGL(fk_ritz, dim3(w_ncA), dim3(AI_BLOCK), 0, sw, (const Task*)coarseP.p, (const SegRec*)wrecP.p, C.m(cd), C.coef(cd), w_mp, C.cu(cd),
+                         (const double*)u1.p, (double* const*)d_slabtab.p, (size_t)W, ev.p, warm ? C.coef2(cd) : (const double*)nullptr,
+                         warm ? C.cu2(cd) : (const double*)nullptr, warm ? ev2.p : (double*)nullptr);
       AI_KERNEL_CHECK();
       // the true residual of every Ritz pair, into pinned memory behind the sweep results (r_true[nA])
       hipLaunchKernelGGL(fk_resid, dim3(w_nfA), dim3(AI_BLOCK), 0, sw, (const Task*)fineP.p, G, (const double*)wm.p, (const double*)sinv2.p,
-                         (const double*)ev.p, th_dev, presid.p);
+                         (const double*)ev.p, C.theta(cd), presid.p);
       AI_KERNEL_CHECK();
-      hipLaunchKernelGGL(fk_resid_final, dim3((unsigned)nA), dim3(AI_BLOCK), 0, sw, (const SegRec*)wrecP.p, (const double2*)presid.p, pr_mcut + 2 * nA);
+      hipLaunchKernelGGL(fk_resid_final, dim3((unsigned)nA), dim3(AI_BLOCK), 0, sw, (const SegRec*)wrecP.p, (const double2*)presid.p, R.rtrue(rw));
       AI_KERNEL_CHECK();
       hipLaunchKernelGGL(fk_minmax, dim3(w_ncA), dim3(AI_BLOCK), 0, sw, (const Task*)coarseP.p, G, (const double*)ev.p, pmm.p);
       AI_KERNEL_CHECK();
@@ -1004,23 +947,24 @@ class Flow {
                          (const uint8_t*)bin.p, psweep.p);
       AI_KERNEL_CHECK();
       hipLaunchKernelGGL(fk_sweep_final, dim3((unsigned)nA), dim3(AI_BLOCK), 0, sw, (const SegRec*)wrecP.p, (const int32_t*)w_nosplit.p,
-                         (const double*)psweep.p, T, pr_i + 2 * nA, pr_i, pr_i + nA, pr_mcut, dump_costs());
+                         (const double*)psweep.p, T, R.kstar(rw), R.split(rw), R.ntrue(rw), R.mcut(rw), dump_costs());
       AI_KERNEL_CHECK();
     }
     if (!wM.empty()) {
-      w_ncomp_all = *(const int32_t*)pin_res();
+      w_ncomp_all = *res_comp_total(pin_res());
       const int len = w_hiM - w_loM;
       if (w_ncomp_all < 2 || w_ncomp_all > len) {
         ai_set_error("internal: %d components in the disconnected segments of a wave with %d rows", w_ncomp_all, len);
         return AI_ERR_INTERNAL;
       }
       // the component table goes straight into pinned memory (the histories' area: the helper thread has read them by now)
-      w_tab_pinned = (size_t)2 * w_ncomp_all * sizeof(int32_t) <= PIN_HIST;
+      const CompTable CT((size_t)w_ncomp_all);
+      w_tab_pinned = CT.fits_pinned();
       int32_t* d_troot;
       int32_t* d_tsize;
       if (w_tab_pinned) {
-        d_troot = (int32_t*)pin_hist();
-        d_tsize = d_troot + w_ncomp_all;
+        d_troot = CT.troot(pin_hist());
+        d_tsize = CT.tsize(pin_hist());
       } else {
         AI_TRY(troot.ensure((size_t)w_ncomp_all));
         AI_TRY(tsize.ensure((size_t)w_ncomp_all));
@@ -1052,14 +996,16 @@ class Flow {
   void guard_dump(const char* tag, size_t i, size_t nA, const FSeg& sg, double resid, double rtrue) {
     FILE* f = fopen(guard_log, "a");
     if (!f) return;
-    const size_t pitch = (size_t)3 * w_mp + FK_HIST_HEAD;
-    const double* row = hist_copy.data() + i * pitch;
-    const double* c = coef_copy.data() + 3 * nA + i * (size_t)w_mp;
+    const HistRows H((size_t)w_mp);
+    const CoefTable C(nA, (size_t)w_mp, false);   // coef_copy holds the first vector's part
+    const double* row = H.row(hist_copy.data(), i);
+    const double* c = C.coef(coef_copy.data(), i);
     fprintf(f, "%s g0 %d n %d m %d restarts %d slot %d chunk %d par %d J %d wave_mp %d dev_theta %a dev_resid %a host_theta %a cu %a est %a true %a\n", tag, sg.g0, sg.n, sg.m,
-            sg.restarts, sg.slot, sg.chunk, sg.par, J, w_mp, row[0], row[1], coef_copy[nA + i], coef_copy[i], resid, rtrue);
+            sg.restarts, sg.slot, sg.chunk, sg.par, J, w_mp, H.theta(row), H.resid(row), C.theta(coef_copy.data())[i], C.cu(coef_copy.data())[i], resid, rtrue);
     const char* names[4] = {"a", "b", "g", "c"};
+    const double* vals[4] = {H.a(row), H.b(row), H.g(row), c};
     for (int k = 0; k < 4; ++k) {
-      const double* v = (k < 3) ? row + FK_HIST_HEAD + (size_t)k * w_mp : c;
+      const double* v = vals[k];
       fprintf(f, "%s", names[k]);
       for (int j = 0; j < sg.m && j < w_mp; ++j) fprintf(f, " %a", v[j]);
       fprintf(f, "\n");
@@ -1113,7 +1059,7 @@ class Flow {
       h.restarts = s.restarts;
       v.resize((size_t)s.n);
       AI_HIP(hipMemcpyAsync(v.data(), ev.p + s.g0, (size_t)s.n * sizeof(double), hipMemcpyDeviceToHost, sw));
-      AI_HIP(hipMemcpyAsync(&h.theta, coef_d.p + wA.size() + wi, sizeof(double), hipMemcpyDeviceToHost, sw));
+      AI_HIP(hipMemcpyAsync(&h.theta, CoefTable(wA.size(), (size_t)w_mp, warm != 0).theta(coef_d.p) + wi, sizeof(double), hipMemcpyDeviceToHost, sw));
       AI_HIP(hipMemcpyAsync(&h.scale, w_scale.p + wi, sizeof(double), hipMemcpyDeviceToHost, sw));
       AI_HIP(hipMemcpyAsync(&ns, w_nosplit.p + wi, sizeof(int32_t), hipMemcpyDeviceToHost, sw));
       AI_HIP(hipMemcpyAsync(h.thr, w_thr.p + (size_t)wi * AI_NUM_CUTS, sizeof h.thr, hipMemcpyDeviceToHost, sw));
@@ -1144,12 +1090,10 @@ class Flow {
     std::vector<FSeg> cbin, ccomp;  // continuing children
     std::vector<int32_t> ccont;
     if (nA) {
-      const int32_t* r_split = (const int32_t*)(pin_res() + 64);
-      const int32_t* r_ntrue = r_split + nA;
-      const int32_t* r_kstar = r_ntrue + nA;
-      const double* r_resid = (const double*)(pin_res() + 64 + (((size_t)3 * nA * sizeof(int32_t) + 15) & ~(size_t)15)) + nA;
-      const double* r_mcut = (const double*)(pin_res() + 64 + (((size_t)3 * nA * sizeof(int32_t) + 15) & ~(size_t)15));
-      const double* r_true = r_mcut + 2 * nA;   // fk_resid_final: ||M ev - theta ev|| / ||ev||
+      const WaveResults R(nA);
+      char* const rw = res_wave(pin_res());
+      const int32_t *r_split = R.split(rw), *r_ntrue = R.ntrue(rw), *r_kstar = R.kstar(rw);
+      const double *r_mcut = R.mcut(rw), *r_resid = R.resid(rw), *r_true = R.rtrue(rw);
       if (trace)
         for (size_t i = 0; i < nA; ++i)
           fprintf(stderr, "[seg] %d %d m=%d theta=%.17g resid=%.6e true=%.6e split=%d ntrue=%d k=%d mcut=%.17g\n", wA[i].g0, wA[i].n, wA[i].m, w_theta[i],
@@ -1159,9 +1103,7 @@ class Flow {
         // a residual above tol is a failure only if T is smaller than the segment's own dimension
         if (r_resid[i] > opt.tol && s.m < s.n - 1) ++stats.unconverged;
         stats.max_resid = std::max(stats.max_resid, r_resid[i]);
-        wslots_to_free.push_back(s.slot);
-        fa.release(s.f0, fk_nf(s.n));
-        ca.release(s.c0, fk_nc(s.n));
+        give_back(s, wslots_to_free);   // (the slot only when the wave is over)
         --chunk_live[s.chunk];
         if (r_resid[i] <= opt.tol && r_true[i] > true_resid_limit && !(s.restarts > 0 && r_true[i] == s.prev_true)) {
           // The check froze this segment as converged, but its Ritz pair is not an eigenpair of the segment's operator: it was built
@@ -1180,19 +1122,7 @@ class Flow {
           if (debug) fprintf(stderr, "[flow] segment %d+%d: Ritz residual estimate %.3g but true residual %.3g: solved again\n", s.g0, s.n, r_resid[i], r_true[i]);
           ++n_restarted;
           --stats.lanczos_solves;
-          FSeg ch;
-          ch.g0 = s.g0;
-          ch.n = s.n;
-          ch.chunk = s.chunk;
-          ch.par = s.par;       // not split: its graph stays where it is
-          ch.vdelta = s.vdelta;
-          ch.binary_child = false;
-          ch.restarts = s.restarts + 1;
-          ch.prev_true = r_true[i];
-          ch.warm_n = s.warm_n;   // (its own harvest wrote ev2 only: warm[] at its rows is still its ancestor's)
-          ch.front = s.front;
-          ch.path = s.path;
-          ccomp.push_back(ch);   // (chunk_live is counted with the other continuing children below)
+          child_solve_again(s, r_true[i], ccomp);   // (chunk_live is counted with the other continuing children below)
           continue;
         }
         if (guard_log && s.restarts > 0 && hist_copy.size()) guard_dump("REPEAT", i, nA, s, r_resid[i], r_true[i]);
@@ -1214,42 +1144,19 @@ class Flow {
           leaf(s.g0, s.front, r_mcut[i]);
           continue;
         }
-        const int na = r_ntrue[i], nb = s.n - na;
-        if (na <= 0 || nb <= 0) {
-          ai_set_error("internal: split of a %d-row segment produced an empty side (%d / %d)", s.n, na, nb);
+        const CutSides cs = children_of_cut(s, r_ntrue[i], r_mcut[i], n_orig[s.chunk], cbin, leaves);
+        if (!cs.ok) {
+          ai_set_error("internal: split of a %d-row segment produced an empty side (%d / %d)", s.n, cs.na, cs.nb);
           return AI_ERR_INTERNAL;
         }
         SplitSeg q{};
         q.g0 = s.g0;
         q.n = s.n;
-        q.ntrue = na;
+        q.ntrue = cs.na;
         q.multi = 0;
         q.kstar = r_kstar[i];
-        q.contA = eligible(na, n_orig[s.chunk], 0.01) ? 1 : 0;
-        q.contB = eligible(nb, n_orig[s.chunk], 0.01) ? 1 : 0;
-        FSeg ch;
-        ch.chunk = s.chunk;
-        ch.par = s.par ^ 1;
-        ch.vdelta = s.vdelta;
-        ch.binary_child = true;
-        ch.warm_n = s.n;   // the children start from this segment's second Ritz vector (fk_partition carries it to their rows)
-        ch.path = std::max(s.path, r_mcut[i]);  // the boundary between the two sides appears once this cut and all its ancestors do
-        if (q.contA) {
-          ch.g0 = s.g0;
-          ch.n = na;
-          ch.front = s.front;
-          cbin.push_back(ch);
-        } else {
-          leaf(s.g0, s.front, NAN);
-        }
-        if (q.contB) {
-          ch.g0 = s.g0 + na;
-          ch.n = nb;
-          ch.front = ch.path;
-          cbin.push_back(ch);
-        } else {
-          leaf(s.g0 + na, ch.path, NAN);
-        }
+        q.contA = cs.contA ? 1 : 0;
+        q.contB = cs.contB ? 1 : 0;
         P2.push_back(s);
         ssv.push_back(q);
       }
@@ -1257,9 +1164,9 @@ class Flow {
     const size_t nP2bin = P2.size();
     if (!wM.empty()) {
       if (w_tab_pinned) {
-        const int32_t* pt = (const int32_t*)pin_hist();
-        h_troot.assign(pt, pt + w_ncomp_all);
-        h_tsize.assign(pt + w_ncomp_all, pt + 2 * (size_t)w_ncomp_all);
+        const CompTable CT((size_t)w_ncomp_all);
+        h_troot.assign(CT.troot(pin_hist()), CT.troot(pin_hist()) + CT.n);
+        h_tsize.assign(CT.tsize(pin_hist()), CT.tsize(pin_hist()) + CT.n);
       } else {
         AI_HIP(hipStreamSynchronize(sw));  // the component table went to pageable memory
       }
@@ -1272,35 +1179,13 @@ class Flow {
           AI_TRY(dump_seg(s, h, -1));
         }
 #endif
-        int offp = 0;
-        const double pcomp = std::max(s.path, 0.0);  // the cut between whole components costs exactly 0
-        while (ti < h_troot.size() && h_troot[ti] < s.g0 + s.n) {
-          const int nc = h_tsize[ti];
-          if (h_troot[ti] < s.g0 || nc <= 0 || offp + nc > s.n) {
-            ai_set_error("internal: component table does not tile a %d-row segment", s.n);
-            return AI_ERR_INTERNAL;
-          }
-          if (eligible(nc, n_orig[s.chunk], 0.01)) {
-            FSeg ch;
-            ch.chunk = s.chunk;
-            ch.par = s.par ^ 1;
-            ch.vdelta = s.vdelta;
-            ch.g0 = s.g0 + offp;
-            ch.n = nc;
-            ch.warm_n = s.warm_n;     // inherited: the last solved ancestor's vector, carried through this split as well
-            ch.binary_child = false;  // connected by construction
-            ch.front = offp ? pcomp : s.front;
-            ch.path = pcomp;
-            ccomp.push_back(ch);
-            ccont[ti] = 1;
-          } else {
-            leaf(s.g0 + offp, offp ? pcomp : s.front, NAN);
-          }
-          offp += nc;
-          ++ti;
+        const CompSplit sp = children_of_components(s, h_troot.data(), h_tsize.data(), h_troot.size(), ti, n_orig[s.chunk], ccont.data(), ccomp, leaves);
+        if (sp.status == COMP_NO_TILE) {
+          ai_set_error("internal: component table does not tile a %d-row segment", s.n);
+          return AI_ERR_INTERNAL;
         }
-        if (offp != s.n) {
-          ai_set_error("internal: components of a segment cover %d of %d rows", offp, s.n);
+        if (sp.status == COMP_SHORT) {
+          ai_set_error("internal: components of a segment cover %d of %d rows", sp.covered, s.n);
           return AI_ERR_INTERNAL;
         }
         SplitSeg q{};
@@ -1323,8 +1208,8 @@ class Flow {
     AI_TRY(retire_chunks());
     if (!P2.empty()) {
       int nfP = 0, ncP = 0;
-      AI_TRY(expand(P2, wrecP, fineP.p, coarseP.p, 0, nfP, ncP, ssv.data(), ss_d.p, ssv.size() * sizeof(SplitSeg), ccont.data(), ccont_d.p,
-                    ccont.size() * sizeof(int32_t)));
+      AI_TRY(expand(P2, wrecP, fineP.p, coarseP.p, 0, nfP, ncP, Rider{ssv.data(), ss_d.p, ssv.size() * sizeof(SplitSeg)},
+                    Rider{ccont.data(), ccont_d.p, ccont.size() * sizeof(int32_t)}));
       int lo = N, hi = 0;
       for (auto& s : P2) {
         lo = std::min(lo, s.g0);
@@ -1390,18 +1275,16 @@ class Flow {
       for (; take < wC.size(); ++take) {
         FSeg& s = wC[take];
         if (free_slots.empty() || (int)take >= room) break;
-        const int f0 = fa.alloc(fk_nf(s.n));
-        const int c0 = (f0 >= 0) ? ca.alloc(fk_nc(s.n)) : -1;
-        if (f0 < 0 || c0 < 0) {
-          if (f0 >= 0) fa.release(f0, fk_nf(s.n));
+        s.f0 = fa.alloc(fk_nf(s.n));
+        s.c0 = (s.f0 >= 0) ? ca.alloc(fk_nc(s.n)) : -1;
+        if (s.f0 < 0 || s.c0 < 0) {
+          give_back(s, free_slots);   // (the fine range, if it got one: it has no slot yet; detached with the others below)
           break;
         }
         s.aux = (int)take;
         s.slot = free_slots.back();
         free_slots.pop_back();
         ((volatile int32_t*)pin_status())[s.slot] = 0;
-        s.f0 = f0;
-        s.c0 = c0;
         s.cap = std::max(1, std::min(opt.max_iter, s.n - 1));
         s.frozen = false;
         s.m = 0;
@@ -1411,8 +1294,7 @@ class Flow {
         for (size_t i = take; i < wC.size(); ++i) {
           FSeg s = wC[i];
           s.binary_child = true;
-          s.slot = -1;
-          s.f0 = s.c0 = -1;
+          s.detach();
           new_roots.push_back(s);
         }
         wC.resize(take);
@@ -1458,7 +1340,7 @@ class Flow {
       hipLaunchKernelGGL(fk_encode, dim3(nfC), dim3(AI_BLOCK), 0, sw, (const Task*)fineC.p, G, ucol.p, lidx.p, enc.p, gate, w_nbin);
       AI_KERNEL_CHECK();
       hipLaunchKernelGGL(fk_reset_slots, dim3(((unsigned)wC.size() + AI_BLOCK - 1) / AI_BLOCK), dim3(AI_BLOCK), 0, sw, (const SegRec*)wrecC.p,
-                         (int)wC.size(), L, s_lastm.p, s_nextm.p, opt.check_every, s_theta.p, s_resid.p, gate, w_nbin, (int32_t*)(pin_res() + 64));
+                         (int)wC.size(), L, s_lastm.p, s_nextm.p, opt.check_every, s_theta.p, s_resid.p, gate, w_nbin, res_child_comps(pin_res()));
       AI_KERNEL_CHECK();
       if (any_pca) {  // ancestor-less segments: warm[] = u1 * principal-axis coordinate, SegRec.pad0 = their own row count
         hipLaunchKernelGGL(fk_pca_moments, dim3(ncC), dim3(AI_BLOCK), 0, sw, (const Task*)coarseC.p, (const SegRec*)wrecC.p, G,
@@ -1490,7 +1372,7 @@ class Flow {
   // the wave is over: connected children start iterating at the step the host has reached; children of a cut that fell
   // apart give their slot back and wait for the next wave, which splits them into their components
   int wave_finish() {
-    const int32_t* r_ncomp = (const int32_t*)(pin_res() + 64);
+    const int32_t* r_ncomp = res_child_comps(pin_res());
     int joined = 0;
     for (size_t i = 0; i < wC.size(); ++i) {
       FSeg s = wC[i];
@@ -1499,11 +1381,8 @@ class Flow {
           ai_set_error("internal: %d components counted in a %d-row child", r_ncomp[i], s.n);
           return AI_ERR_INTERNAL;
         }
-        free_slots.push_back(s.slot);
-        fa.release(s.f0, fk_nf(s.n));
-        ca.release(s.c0, fk_nc(s.n));
-        s.slot = -1;
-        s.f0 = s.c0 = -1;
+        give_back(s, free_slots);
+        s.detach();
         // the cut between whole components costs exactly 0, and the reference splits iff mcut < T (normalized_cut.py:56)
         if (T > 0.0) {
           pend_multi.push_back(s);

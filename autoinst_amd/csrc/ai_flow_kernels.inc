@@ -287,7 +287,7 @@ struct __attribute__((aligned(16))) CTask {       // 512-row task of the update
   int32_t vdelta;
 };
 
-#define FK_HIST_HEAD 4   // doubles in front of a packed history row: theta, resid, m, checksum (fk_pack_hist)
+// FK_HIST_HEAD (doubles in front of a packed history row: theta, resid, m, checksum) comes from ai_flow_host.h with the rows' layout
 struct FlowLz {
   int32_t* frozen;      // [slot]
   int32_t* m;           // [slot] size of T at freeze

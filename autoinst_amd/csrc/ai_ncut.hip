@@ -16,6 +16,7 @@
 #include "ai_common.h"
 
 #include "ai_dense_sym.h"
+#include "ai_flow_host.h"
 #include "ai_ncut_params.h"
 #include "ai_ncut_shared.h"
 #include "ai_tridiag.h"

@@ -40,11 +40,6 @@ static double now_ms() {
   return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
-static bool eligible(int n, int64_t n_orig, double split_lim) {
-  // normalized_cut.py:39-40: W.shape[0] > 2 and len(labels) / (num_points_orig + 1e-8) > split_lim
-  return n > 2 && ((double)n / ((double)n_orig + 1e-8)) > split_lim;
-}
-
 // fixed-order sum of part[t0..t1) by one block; every thread returns the same value
 __device__ __forceinline__ double ai_range_sum(const double* __restrict__ part, int t0, int t1, double* sm) {
   double a = 0.0;
